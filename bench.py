@@ -5,6 +5,10 @@ synthetic object already resident in HBM.  Weak scaling: every rank holds `--obj
 (default 8 GiB = BASELINE configs[1]); at N GPUs the object is N x 8 GiB, sharded by aligned
 chunk ranges, with one RCCL all-gather of subtree roots before rank 0's final levels.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps, writes the last
+step's root with --dump-outputs DIR, and prints the headline with the K1 roofline its own timed
+steps give.  Everything else below is measured only with --full.
+
 Rank 0 prints ONE JSON line on stdout, last, at most LINE_MAX_BYTES (compact_line): the headline,
 the K1 roofline (HIP events on the launch stream over the timed region), the CPU baseline (the
 oracle's faithful serial restatement of common/hashtree timed on this host over the same bytes),
@@ -73,6 +77,16 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="object workload: after the headline also run everything else the line can carry (the "
+                         "CPU baseline and full-size parity, the measured read peak, the host-buffer rates, the "
+                         "sweep points, the other configs and the latency block at N = 1; the exchange timing, "
+                         "the parity legs, the strong-scaling, configs[3]/[4] and in-process legs at N > 1).  "
+                         "Without it the run sets up, warms up, times --steps steps and prints the headline "
+                         "line with the roofline its own timed steps give")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="object workload: after the timed steps write what the last timed step returned to its "
+                         "caller (the 32-byte Merkle root, one float32 per byte) as DIR/root.npy")
     ap.add_argument("--object-gib", type=float, default=8.0, help="object bytes per GPU (GiB), weak scaling")
     ap.add_argument("--total-gib", type=float, default=0.0,
                     help="object bytes across all ranks (GiB); 1024 at --gpus 8 = BASELINE configs[3] "
@@ -146,6 +160,11 @@ def main() -> None:
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--watchdog-check", type=float, default=0.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "object":
+        ap.error("--dump-outputs belongs to the object workload (the headline)")
+    if not args.full and args.workload == "object":
+        # the plain run is the headline alone; an explicit --sweep or --e2e still adds its own block
+        args.no_cpu = args.no_extras = args.no_strong = args.no_verify = True
 
     if args.gpus > 1 and os.environ.get("WORLD_SIZE") in (None, ""):
         # no launcher: start the rank processes here, before anything touches torch or the GPU
@@ -221,11 +240,13 @@ def main() -> None:
     decide = (lambda mine: mine) if world == 1 else (lambda mine: _bcast_flag(torch, dist, mine, wait_group))
     detail = args.detail_out or os.path.join(ROOT, "gpurun_out", f"bench_detail_n{1 if args.same_device else world}.json")
     progress("headline: timed steps")
-    out = run_object(args, torch, dist, world, rank, device, dev_index, gloo, barrier, cpu_leg=not args.no_cpu)
+    out = run_object(args, torch, dist, world, rank, device, dev_index, gloo, barrier, cpu_leg=not args.no_cpu,
+                     dump_dir=args.dump_outputs)
     if isinstance(out.get("parity"), dict):
         out["parity"]["pinned_by"] = PIN_MERKLE
     if world > 1:
         out["launch"] = launch_info(torch, dist, world, rank, local_rank, dev_index, args)
+    if world > 1 and args.full:
         progress("exchange: the all-gather of subtree roots alone")
         out["exchange"] = measure_exchange(plan_shards(out["config"]["object_bytes"], args.chunk, world), torch,
                                            dist, device, gloo, barrier)
@@ -647,11 +668,20 @@ def launch_info(torch, dist, world, rank, local_rank, dev_index, args):
             "launcher": os.environ.get("DEOSS_BENCH_LAUNCHER", "external (WORLD_SIZE set by the caller's launcher)")}
 
 
-def run_object(args, torch, dist, world, rank, device, dev_index, gloo, barrier, cpu_leg=False):
+def dump_outputs(dump_dir, root_bytes):
+    """--dump-outputs DIR: what the timed path's last step handed its caller -- the 32-byte Merkle
+    root -- as DIR/root.npy, one float32 per byte, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "root.npy"), np.frombuffer(root_bytes, dtype=np.uint8).astype(np.float32))
+
+
+def run_object(args, torch, dist, world, rank, device, dev_index, gloo, barrier, cpu_leg=False, dump_dir=""):
     """One object over all ranks (BASELINE configs[1] at N = 1, the weak-scaling curve, configs[3]
-    with --total-gib 1024): timed steps, roofline, parity legs; with cpu_leg, the CPU baseline
-    (N = 1: over the whole object; N > 1: over rank 0's shard).  Returns rank 0's line (other ranks
-    get theirs too, unused).  Buffers are released before returning."""
+    with --total-gib 1024): timed steps, roofline, and with --full the measured read peak and the
+    parity legs; with cpu_leg, the CPU baseline (N = 1: over the whole object; N > 1: over rank 0's
+    shard); with dump_dir, rank 0 writes the last timed step's root there (dump_outputs).  Returns
+    rank 0's line (other ranks get theirs too, unused).  Buffers are released before returning."""
     from deoss_amd import MerkleContext, plan_shards
     from deoss_amd.sharding import sharded_root
     chunk = args.chunk
@@ -701,9 +731,12 @@ def run_object(args, torch, dist, world, rank, device, dev_index, gloo, barrier,
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     root_hex = bytes(root_dev.cpu().numpy()).hex() if rank == 0 else None
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, bytes.fromhex(root_hex))
 
     value = total * args.steps / elapsed / (1 << 30)
-    read_peak_gbs, read_peak_ms = measure_read_peak(ctx, torch, buf, local_len, sptr, stream)
+    read_peak_gbs, read_peak_ms = (measure_read_peak(ctx, torch, buf, local_len, sptr, stream) if args.full
+                                   else (None, None))
     cpu_out = {}
     if world > 1 and rank == 0 and cpu_leg:
         # N > 1: the CPU baseline over rank 0's shard (at most 8 GiB of whole leaves), copied back
@@ -1330,12 +1363,13 @@ def cpu_baseline_over(torch, buf, length, chunk, out, total, what):
 
 
 def extras(args, ctx, torch, buf, length, chunk, root_hex, out, sptr):
+    do_e2e = (args.e2e or not args.no_extras) and not args.no_e2e
+    if args.no_cpu and not do_e2e and (args.no_sweep or (args.no_extras and not args.sweep)):
+        return   # the plain run: nothing beside the headline, the CPU checker is not even loaded
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import numpy as np
     from oracle import Oracle   # CPU baseline / checker only
     orc = Oracle()
     host = None
-    do_e2e = (args.e2e or not args.no_extras) and not args.no_e2e
     if not args.no_cpu or do_e2e:
         host = torch.empty(length, dtype=torch.uint8, pin_memory=True)
         host.copy_(buf[:length])

@@ -59,3 +59,14 @@ def test_cpu_baseline_legs_small():
     f = bench.cpu_fp_baseline(orc, a.ctypes.data, a.size, 1 << 20, "a test buffer", serial_segs=1, par_segs=3)
     assert f["cores"] == 1 and f["value"] > 0 and "1 segment(s)" in f["sample"]
     assert f["parallel"]["value"] > 0 and "3 segments" in f["parallel"]["sample"]
+
+
+def test_dump_outputs_writes_the_root_as_float32(tmp_path):
+    """--dump-outputs: the timed path's one output, the 32-byte root, as DIR/root.npy -- float32, one
+    value per byte, so the bytes come back exactly; DIR is created when missing."""
+    root = bytes(range(224, 256))
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), root)
+    assert sorted(os.listdir(d)) == ["root.npy"]
+    a = np.load(d / "root.npy")
+    assert a.dtype == np.float32 and a.shape == (32,) and bytes(a.astype(np.uint8)) == root

@@ -8,5 +8,5 @@
 set -e
 n=${1:-8}
 export TMPDIR=/tmp
-python bench.py --gpus $n --dist-backend gloo --same-device --object-gib 0.25 --steps 2 --multi-configs \
+python bench.py --full --gpus $n --dist-backend gloo --same-device --object-gib 0.25 --steps 2 --multi-configs \
   --cfg3-total-gib 8 --cfg4-objects 8000 --prefix-gib 1 --in-process --inproc-gib 16
