@@ -1,0 +1,592 @@
+// restore_capi.inl -- the download side on the GPU (dm_rs_restore_*, dm_restore_buffer,
+// dm_retrieve_file; include/deoss_merkle.h).  Part of merkle_capi.hip (after fullproc_capi.inl;
+// shares dm_ctx, Dev, dm_rs, the leaf launches and the file helpers).
+//
+// Replaces the RSRestore / join / truncate part of cess-go-sdk process.Retrievefile(chainer, fmeta,
+// fid, dir, cipher = "") (node/fileHandler.go:519,600,990): for every segment any chain.DataShards
+// of its fragments rebuild the data fragments, the segments are joined and the zero padding is cut
+// off at the file size.  Here, per call (or per window of segments):
+//   1. fragments go to HBM: data fragments straight to their final place in the object, parity
+//      fragments to scratch;
+//   2. (DM_RESTORE_VERIFY_FRAGMENTS) ONE table-mode leaf launch hashes every fragment given; a
+//      fragment whose SHA-256 is not its name is bad and the next good one takes its place;
+//   3. ONE rs_restore_kernel launch rebuilds every segment, each with its own erasure pattern
+//      (one coding table per distinct pattern, uploaded once);
+//   4. (DM_RESTORE_VERIFY_SEGMENTS / _FID) one leaf launch hashes the restored segments, the
+//      digests reduce to the fid;
+//   5. the object's bytes leave the device only when everything asked for held.
+
+namespace {
+
+constexpr uint64_t kRtWindowBytes = 1ull << 30;   // dm_retrieve_file: segment bytes per GPU pass (+ 2x parity scratch)
+constexpr int kRtReaders = 8;                      // fragment files read at once into a pinned slot
+
+struct RestorePlan {
+    int inputs[dm::kRsMaxIn];
+    int outputs[dm::kRsMaxIn];
+    int nout = 0;
+    uint8_t rows[dm::kRsMaxIn * dm::kRsMaxIn];   // nout x k
+};
+
+// The plan of one pattern (klauspost's rule, as rs_decode_plan): the first k present fragments in
+// index order are read; every data fragment that is missing or not at its final address is
+// written, fragment j with row j of the inverse of the inputs' sub-matrix (a unit row when j is
+// itself an input: a present data fragment always is).
+int restore_plan(dm_ctx* c, const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* in_place,
+                 RestorePlan& p) {
+    const int total = k + m;
+    int nv = 0;
+    for (int i = 0; i < total && nv < k; i++)
+        if (present[i]) p.inputs[nv++] = i;
+    if (nv < k) return fail(c, DM_ERR_INVALID, "too few shards given (%d of %d needed)", nv, k);
+    uint8_t sub[dm::kRsMaxIn * dm::kRsMaxIn], inv[dm::kRsMaxIn * dm::kRsMaxIn];
+    for (int i = 0; i < k; i++) std::memcpy(sub + i * k, mat + p.inputs[i] * k, (size_t)k);
+    if (!gf_invert(sub, k, inv)) return fail(c, DM_ERR_INVALID, "singular decode matrix");
+    p.nout = 0;
+    for (int j = 0; j < k; j++) {
+        if (present[j] && in_place && in_place[j]) continue;
+        p.outputs[p.nout] = j;
+        std::memcpy(p.rows + p.nout * k, inv + j * k, (size_t)k);
+        p.nout++;
+    }
+    return DM_OK;
+}
+
+// Descriptors and coding tables of one restore launch, built segment by segment.
+struct RestoreBatch {
+    struct Cached {
+        RestorePlan p;
+        uint32_t tab;
+    };
+    std::vector<dm::RsRestoreDesc> desc;
+    std::vector<uint64_t> tabs;                 // [ntab][k][256]
+    std::map<uint32_t, Cached> plans;           // present mask | in-place mask << 16
+    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index (one table per distinct plan)
+    bool any_out = false;
+};
+
+// Segment whose usable fragments are frags[0 .. total) (device addresses, NULL = absent) and whose
+// data fragment j belongs at seg_base + j * frag.
+int restore_add(dm_rs* r, RestoreBatch& b, const uint8_t* const* frags, uint8_t* seg_base, uint64_t frag) {
+    const int k = r->k, total = r->k + r->m;
+    uint8_t present[dm::kRsMaxIn + dm::kRsMaxOut], in_place[dm::kRsMaxIn];
+    uint32_t key = 0;
+    for (int j = 0; j < total; j++) {
+        present[j] = frags[j] != nullptr;
+        key |= (uint32_t)present[j] << j;
+        if (j < k) {
+            in_place[j] = frags[j] == seg_base + (uint64_t)j * frag;
+            key |= (uint32_t)in_place[j] << (16 + j);
+        }
+    }
+    auto it = b.plans.find(key);
+    if (it == b.plans.end()) {
+        RestoreBatch::Cached cp;
+        RC_TRY(restore_plan(r->c, r->mat.data(), k, r->m, present, in_place, cp.p));
+        cp.tab = 0;
+        if (cp.p.nout) {
+            const std::string rows(reinterpret_cast<const char*>(cp.p.rows), (size_t)cp.p.nout * k);
+            auto t = b.tab_of.find(rows);
+            if (t == b.tab_of.end()) {
+                const std::vector<uint64_t> tab = rs_table(cp.p.rows, cp.p.nout, k);
+                t = b.tab_of.emplace(rows, (uint32_t)(b.tabs.size() / ((size_t)k * 256))).first;
+                b.tabs.insert(b.tabs.end(), tab.begin(), tab.end());
+            }
+            cp.tab = t->second;
+        }
+        it = b.plans.emplace(key, cp).first;
+    }
+    const RestorePlan& p = it->second.p;
+    dm::RsRestoreDesc ds{};
+    for (int j = 0; j < k; j++) ds.in[j] = frags[p.inputs[j]];
+    for (int i = 0; i < p.nout; i++) ds.out[i] = seg_base + (uint64_t)p.outputs[i] * frag;
+    ds.nout = (uint32_t)p.nout;
+    ds.table = it->second.tab;
+    if (p.nout) b.any_out = true;
+    b.desc.push_back(ds);
+    return DM_OK;
+}
+
+int restore_launch(dm_rs* r, Dev& d, hipStream_t s, const RestoreBatch& b, uint64_t units) {
+    dm_ctx* c = r->c;
+    if (!b.any_out) return DM_OK;
+    RsLane& L = rs_ln(r, d);
+    const uint64_t dbytes = b.desc.size() * sizeof(dm::RsRestoreDesc), tbytes = b.tabs.size() * 8;
+    RC_TRY(tables_begin(c, d, dbytes + tbytes + 1024));
+    RC_TRY(upload(c, d, s, L.rst_desc, b.desc.data(), dbytes));
+    RC_TRY(upload(c, d, s, L.rst_tab, b.tabs.data(), tbytes));
+    dm::RsRestoreArgs a{};
+    a.desc = static_cast<const dm::RsRestoreDesc*>(L.rst_desc.p);
+    a.tables = static_cast<const uint2*>(L.rst_tab.p);
+    a.units_per_seg = units;
+    a.nseg = b.desc.size();
+    const dim3 grid = rs_grid(d, units, a.nseg), block(dm::kRsThreads);
+    switch (r->k) {
+        case 1: hipLaunchKernelGGL(dm::rs_restore_kernel<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(dm::rs_restore_kernel<2>, grid, block, 0, s, a); break;
+        case 3: hipLaunchKernelGGL(dm::rs_restore_kernel<3>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(dm::rs_restore_kernel<4>, grid, block, 0, s, a); break;
+        case 5: hipLaunchKernelGGL(dm::rs_restore_kernel<5>, grid, block, 0, s, a); break;
+        case 6: hipLaunchKernelGGL(dm::rs_restore_kernel<6>, grid, block, 0, s, a); break;
+        case 7: hipLaunchKernelGGL(dm::rs_restore_kernel<7>, grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL(dm::rs_restore_kernel<8>, grid, block, 0, s, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return DM_OK;
+}
+
+// SHA-256 of `addrs.size()` device ranges of `len` bytes each (16-byte aligned), one table-mode leaf
+// launch; the digests stay in d.leaves and are copied to `dig` (synchronises s).
+int rt_hash(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<uint64_t>& addrs, uint64_t len,
+            std::vector<uint8_t>& dig) {
+    const uint64_t T = addrs.size();
+    dig.resize(32 * T);
+    if (T == 0) return DM_OK;
+    const std::vector<uint64_t> lens(T, len);
+    RC_TRY(tables_begin(c, d, T * 16 + 1024));
+    HIP_TRY(d.leaves.ensure(T * 32));
+    RC_TRY(upload(c, d, s, d.tab_addr, addrs.data(), T * 8));
+    RC_TRY(upload(c, d, s, d.tab_len, lens.data(), T * 8));
+    dm::LeafArgs la{};
+    la.addrs = static_cast<const uint64_t*>(d.tab_addr.p);
+    la.lens = static_cast<const uint64_t*>(d.tab_len.p);
+    la.nleaves = T;
+    la.byte_end = ~0ull;
+    la.digests = d.leaves.u8();
+    RC_TRY(launch_leaves(c, d, s, la, true, true, pick_leaf_kernel(c, d, T)));
+    HIP_TRY(hipMemcpyAsync(dig.data(), d.leaves.p, 32 * T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DM_OK;
+}
+
+// hashtree root over n segment digests (host) -> root (host); synchronises s.
+int rt_fid(dm_ctx* c, Dev& d, hipStream_t s, const uint8_t* segd, uint64_t n, uint8_t root[32]) {
+    HIP_TRY(d.leaves.ensure(32 * n));
+    HIP_TRY(d.root.ensure(32));
+    HIP_TRY(hipMemcpyAsync(d.leaves.p, segd, 32 * n, hipMemcpyHostToDevice, s));
+    RC_TRY(finish(c, d, s, d.leaves.u8(), n, true, d.root.u8()));
+    HIP_TRY(hipMemcpyAsync(root, d.root.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DM_OK;
+}
+
+enum : uint8_t { kFragAbsent = 0, kFragUsed = 1, kFragSpare = 2, kFragBad = 3 };
+enum : uint8_t { kSegOk = 0, kSegTooFew = 1, kSegMismatch = 2 };
+
+// Fragment states of ns segments -> statuses: the first k good fragments of a segment are used, the
+// other good ones spare; a segment with fewer than k good ones is kSegTooFew (its good fragments
+// stay spare: nothing is rebuilt from them).  `good` holds 1 for a fragment that is on the device
+// and passed its check.  Returns false when any segment has too few.
+bool rt_select(int k, int total, uint64_t ns, const uint8_t* good, uint8_t* fst, uint8_t* sst) {
+    bool all = true;
+    for (uint64_t t = 0; t < ns; t++) {
+        int ng = 0;
+        for (int j = 0; j < total; j++) ng += good[t * total + j];
+        const bool enough = ng >= k;
+        if (!enough) {
+            sst[t] = kSegTooFew;
+            all = false;
+        }
+        int used = 0;
+        for (int j = 0; j < total; j++)
+            if (good[t * total + j]) fst[t * total + j] = (enough && used++ < k) ? kFragUsed : kFragSpare;
+    }
+    return all;
+}
+
+int restore_check(dm_rs* r, uint64_t nseg, uint64_t size, uint64_t segment) {
+    dm_ctx* c = r->c;
+    if (nseg == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
+    RC_TRY(process_check(r, size ? size : 1, segment));
+    if (size <= (nseg - 1) * segment || size > nseg * segment)
+        return fail(c, DM_ERR_INVALID, "size %llu does not end in the last of %llu segments of %llu bytes",
+                    (unsigned long long)size, (unsigned long long)nseg, (unsigned long long)segment);
+    return DM_OK;
+}
+
+int restore_buffer(dm_rs* r, Dev& d, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
+                   const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, void* out,
+                   uint8_t* fst, uint8_t* sst, int* ok) {
+    dm_ctx* c = r->c;
+    hipStream_t s = d.stream;
+    RC_TRY(begin_call(c, d, s));
+    const int k = r->k, total = r->k + r->m;
+    const uint64_t frag = segment / (uint64_t)k, NF = nseg * (uint64_t)total;
+    // 1. data fragments to their final place, parity fragments to scratch
+    uint64_t npar = 0;
+    for (uint64_t t = 0; t < nseg; t++)
+        for (int j = k; j < total; j++) npar += frags[t * total + j] != nullptr;
+    HIP_TRY(d.data.ensure(nseg * segment + kAlign));
+    DevBuf& work = rs_ln(r, d).work;
+    HIP_TRY(work.ensure(npar * frag + 16));
+    std::vector<const uint8_t*> dev(NF, nullptr);
+    std::vector<uint8_t> good(NF, 0);
+    std::vector<uint64_t> addrs, which;
+    uint64_t slot = 0;
+    for (uint64_t t = 0; t < nseg; t++)
+        for (int j = 0; j < total; j++) {
+            const uint64_t i = t * total + j;
+            if (!frags[i]) continue;
+            uint8_t* to = j < k ? d.data.u8() + t * segment + (uint64_t)j * frag : work.u8() + (slot++) * frag;
+            HIP_TRY(hipMemcpyAsync(to, frags[i], frag, hipMemcpyHostToDevice, s));
+            dev[i] = to;
+            good[i] = 1;
+            addrs.push_back(reinterpret_cast<uint64_t>(to));
+            which.push_back(i);
+        }
+    // 2. every supplied fragment against its name
+    if ((flags & DM_RESTORE_VERIFY_FRAGMENTS) && frag_names) {
+        std::vector<uint8_t> dig;
+        RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
+        for (size_t q = 0; q < which.size(); q++)
+            if (std::memcmp(dig.data() + 32 * q, frag_names + 32 * which[q], 32) != 0) {
+                good[which[q]] = 0;
+                fst[which[q]] = kFragBad;
+            }
+    }
+    // 3. plans from the good set, one restore launch
+    if (!rt_select(k, total, nseg, good.data(), fst, sst)) return DM_OK;
+    RestoreBatch b;
+    std::vector<const uint8_t*> use((size_t)total);
+    for (uint64_t t = 0; t < nseg; t++) {
+        for (int j = 0; j < total; j++) use[j] = good[t * total + j] ? dev[t * total + j] : nullptr;
+        RC_TRY(restore_add(r, b, use.data(), d.data.u8() + t * segment, frag));
+    }
+    RC_TRY(restore_launch(r, d, s, b, frag / 16));
+    // 4. the restored segments against their names, their tree against the fid
+    const bool vseg = (flags & DM_RESTORE_VERIFY_SEGMENTS) && seg_names, vfid = (flags & DM_RESTORE_VERIFY_FID) && fid;
+    bool all = true;
+    if (vseg || vfid) {
+        std::vector<uint64_t> sa(nseg);
+        for (uint64_t t = 0; t < nseg; t++) sa[t] = reinterpret_cast<uint64_t>(d.data.u8() + t * segment);
+        std::vector<uint8_t> segd;
+        RC_TRY(rt_hash(c, d, s, sa, segment, segd));
+        if (vseg)
+            for (uint64_t t = 0; t < nseg; t++)
+                if (std::memcmp(segd.data() + 32 * t, seg_names + 32 * t, 32) != 0) {
+                    sst[t] = kSegMismatch;
+                    all = false;
+                }
+        if (vfid && all) {
+            uint8_t root[32];
+            RC_TRY(rt_fid(c, d, s, segd.data(), nseg, root));
+            if (std::memcmp(root, fid, 32) != 0) all = false;
+        }
+    }
+    if (!all) return DM_OK;
+    // 5. everything held: the object's bytes, without the padding
+    HIP_TRY(hipMemcpyAsync(out, d.data.p, size, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *ok = 1;
+    return DM_OK;
+}
+
+std::atomic<uint64_t> g_rt_seq{0};
+
+struct RtLoad {            // one fragment file to bring to the device
+    uint64_t idx;          // window-local t * total + j
+    std::string path;
+    uint8_t* to;
+};
+
+// Fragment files -> pinned slots (parallel preads) -> HBM, slot by slot; synchronises d.copy.
+int rt_load(dm_rs* r, Dev& d, const std::vector<RtLoad>& loads, uint64_t frag, uint64_t slot_cap, FpEvents& ev,
+            uint64_t& next_slot) {
+    dm_ctx* c = r->c;
+    RsLane& L = rs_ln(r, d);
+    const uint64_t per = std::max<uint64_t>(1, slot_cap / frag);
+    for (size_t g0 = 0; g0 < loads.size(); g0 += per) {
+        const size_t n = std::min<size_t>(per, loads.size() - g0);
+        const int sl = (int)(next_slot++ % kFpSlots);
+        HIP_TRY(hipEventSynchronize(ev.slot[sl]));   // the slot's previous copies have left it
+        uint8_t* buf = L.fp_slot[sl].u8();
+        const size_t J = std::min<size_t>(kRtReaders, n);
+        std::vector<std::future<std::string>> jobs;
+        for (size_t j = 0; j < J; j++)
+            jobs.push_back(std::async(std::launch::async, [&, j]() -> std::string {
+                for (size_t i = j; i < n; i += J) {
+                    const std::string& p = loads[g0 + i].path;
+                    const int fd = ::open(p.c_str(), O_RDONLY | O_CLOEXEC);
+                    if (fd < 0) return "open " + p + ": " + go_errno(errno);
+                    uint64_t done = 0;
+                    while (done < frag) {
+                        const ssize_t got = ::pread(fd, buf + i * frag + done, frag - done, (off_t)done);
+                        if (got < 0 && errno == EINTR) continue;
+                        if (got <= 0) {
+                            const std::string e = got < 0 ? go_errno(errno) : std::string("unexpected EOF");
+                            ::close(fd);
+                            return "read " + p + ": " + e;
+                        }
+                        done += (uint64_t)got;
+                    }
+                    ::close(fd);
+                }
+                return std::string();
+            }));
+        std::string err;
+        for (auto& j : jobs) {
+            const std::string e = j.get();
+            if (err.empty()) err = e;
+        }
+        if (!err.empty()) return fail(c, DM_ERR_IO, "%s", err.c_str());
+        for (size_t i = 0; i < n; i++)
+            HIP_TRY(hipMemcpyAsync(loads[g0 + i].to, buf + i * frag, frag, hipMemcpyHostToDevice, d.copy));
+        HIP_TRY(hipEventRecord(ev.slot[sl], d.copy));
+    }
+    HIP_TRY(hipStreamSynchronize(d.copy));
+    return DM_OK;
+}
+
+int rt_write_all(dm_ctx* c, int fd, const std::string& path, const uint8_t* p, uint64_t len, uint64_t off) {
+    uint64_t done = 0;
+    while (done < len) {
+        const ssize_t w = ::pwrite(fd, p + done, len - done, (off_t)(off + done));
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) return fail(c, DM_ERR_IO, "write %s: %s", path.c_str(), go_errno(w < 0 ? errno : EIO).c_str());
+        done += (uint64_t)w;
+    }
+    return DM_OK;
+}
+
+// Everything of dm_retrieve_file but the temporary file's fate; *ok = 1 when the object was
+// restored, verified as asked and written to out_fd.
+int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* frag_names, const uint8_t* seg_names,
+                     const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, int out_fd,
+                     const std::string& out_name, uint8_t* fst, uint8_t* sst, int* ok) {
+    dm_ctx* c = r->c;
+    RsLane& L = rs_ln(r, d);
+    hipStream_t s = d.stream;
+    RC_TRY(begin_call(c, d, s));
+    const int k = r->k, m = r->m, total = k + m;
+    const uint64_t frag = segment / (uint64_t)k;
+    // test hooks (env, read per call): small windows and slots exercise several windows and slot reuse
+    const uint64_t win = std::max<uint64_t>(1, env_bytes("DEOSS_RT_WINDOW_BYTES", kRtWindowBytes) / segment);
+    const uint64_t slot_cap = std::max(env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes), frag);
+    for (auto& b : L.fp_slot) HIP_TRY(b.ensure(slot_cap));
+    FpEvents ev;
+    for (auto& e : ev.slot) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    uint64_t next_slot = 0;
+    const bool vfrag = (flags & DM_RESTORE_VERIFY_FRAGMENTS) != 0;
+    const bool vseg = (flags & DM_RESTORE_VERIFY_SEGMENTS) && seg_names, vfid = (flags & DM_RESTORE_VERIFY_FID) && fid;
+    std::vector<uint8_t> segd_all(vfid ? 32 * nseg : 0);
+    bool all = true;
+    for (uint64_t w0 = 0; w0 < nseg; w0 += win) {
+        const uint64_t ns = std::min(win, nseg - w0), NF = ns * (uint64_t)total;
+        HIP_TRY(hipStreamSynchronize(s));   // the previous window's kernels are done with the object buffer
+        HIP_TRY(d.data.ensure(ns * segment + kAlign));
+        HIP_TRY(L.work.ensure(ns * (uint64_t)m * frag + 16));
+        std::vector<const uint8_t*> dev(NF, nullptr);
+        std::vector<uint8_t> good(NF, 0);
+        std::vector<int> cand(ns, 0), ngood(ns, 0);
+        uint8_t* wf = fst + w0 * total;
+        // 1 + 2. per segment the first k fragment files that exist; further ones while a check fails
+        for (;;) {
+            std::vector<RtLoad> loads;
+            for (uint64_t t = 0; t < ns; t++) {
+                int need = k - ngood[t];
+                while (need > 0 && cand[t] < total) {
+                    const int j = cand[t]++;
+                    const uint64_t i = t * total + j;
+                    const std::string p = dir + "/" + hex32(frag_names + 32 * ((w0 + t) * total + j));
+                    struct stat st {};
+                    if (::stat(p.c_str(), &st) != 0) {
+                        if (errno == ENOENT || errno == ENOTDIR) continue;   // not downloaded: absent
+                        return fail(c, DM_ERR_IO, "stat %s: %s", p.c_str(), go_errno(errno).c_str());
+                    }
+                    if (!S_ISREG(st.st_mode) || (uint64_t)st.st_size != frag) {
+                        wf[i] = kFragBad;   // not a fragment of this object's shape
+                        continue;
+                    }
+                    uint8_t* to = j < k ? d.data.u8() + t * segment + (uint64_t)j * frag
+                                        : L.work.u8() + (t * (uint64_t)m + (uint64_t)(j - k)) * frag;
+                    loads.push_back({i, p, to});
+                    need--;
+                }
+            }
+            if (loads.empty()) break;
+            RC_TRY(rt_load(r, d, loads, frag, slot_cap, ev, next_slot));
+            std::vector<uint8_t> dig;
+            if (vfrag) {
+                std::vector<uint64_t> addrs(loads.size());
+                for (size_t q = 0; q < loads.size(); q++) addrs[q] = reinterpret_cast<uint64_t>(loads[q].to);
+                RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
+            }
+            for (size_t q = 0; q < loads.size(); q++) {
+                const uint64_t i = loads[q].idx;
+                if (vfrag && std::memcmp(dig.data() + 32 * q, frag_names + 32 * (w0 * total + i), 32) != 0) {
+                    wf[i] = kFragBad;
+                    continue;
+                }
+                good[i] = 1;
+                dev[i] = loads[q].to;
+                ngood[i / total]++;
+            }
+        }
+        if (!rt_select(k, total, ns, good.data(), wf, sst + w0)) {
+            all = false;   // nothing of this window is rebuilt; later windows still report their fragments
+            continue;
+        }
+        // 3. one restore launch over the window
+        RestoreBatch b;
+        std::vector<const uint8_t*> use((size_t)total);
+        for (uint64_t t = 0; t < ns; t++) {
+            for (int j = 0; j < total; j++) use[j] = good[t * total + j] ? dev[t * total + j] : nullptr;
+            RC_TRY(restore_add(r, b, use.data(), d.data.u8() + t * segment, frag));
+        }
+        RC_TRY(restore_launch(r, d, s, b, frag / 16));
+        // 4. segment names
+        if (vseg || vfid) {
+            std::vector<uint64_t> sa(ns);
+            for (uint64_t t = 0; t < ns; t++) sa[t] = reinterpret_cast<uint64_t>(d.data.u8() + t * segment);
+            std::vector<uint8_t> segd;
+            RC_TRY(rt_hash(c, d, s, sa, segment, segd));
+            if (vseg)
+                for (uint64_t t = 0; t < ns; t++)
+                    if (std::memcmp(segd.data() + 32 * t, seg_names + 32 * (w0 + t), 32) != 0) {
+                        sst[w0 + t] = kSegMismatch;
+                        all = false;
+                    }
+            if (vfid) std::memcpy(segd_all.data() + 32 * w0, segd.data(), 32 * ns);
+        }
+        if (!all) continue;
+        // 5. the window's bytes through the pinned slots into the output file, cut at the file size
+        const uint64_t wbeg = w0 * segment, wend = std::min(size, (w0 + ns) * segment);
+        for (uint64_t o = wbeg; o < wend; o += slot_cap) {
+            const uint64_t n = std::min(slot_cap, wend - o);
+            const int sl = (int)(next_slot++ % kFpSlots);
+            HIP_TRY(hipEventSynchronize(ev.slot[sl]));
+            HIP_TRY(hipMemcpyAsync(L.fp_slot[sl].p, d.data.u8() + (o - wbeg), n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            RC_TRY(rt_write_all(c, out_fd, out_name, L.fp_slot[sl].u8(), n, o));
+        }
+    }
+    if (all && vfid) {
+        uint8_t root[32];
+        RC_TRY(rt_fid(c, d, s, segd_all.data(), nseg, root));
+        if (std::memcmp(root, fid, 32) != 0) all = false;
+    }
+    *ok = all ? 1 : 0;
+    return DM_OK;
+}
+
+std::mutex g_plan_mu;
+std::map<int, std::vector<uint8_t>> g_plan_mats;   // data * 16 + parity -> coding matrix
+
+}  // namespace
+
+extern "C" {
+
+int dm_rs_restore_plan(int data, int parity, const uint8_t* present, const uint8_t* in_place, int* inputs,
+                       int* outputs, uint8_t* rows, int* nout) {
+    if (!present || !inputs || !outputs || !rows || !nout) return bad_arg();
+    if (data < 1 || data > dm::kRsMaxIn || parity < 1 || parity > dm::kRsMaxOut)
+        return fail(nullptr, DM_ERR_INVALID, "shard counts: 1 <= data <= %d, 1 <= parity <= %d", dm::kRsMaxIn,
+                    dm::kRsMaxOut);
+    std::vector<uint8_t> mat;
+    {
+        std::lock_guard<std::mutex> lk(g_plan_mu);
+        std::vector<uint8_t>& cached = g_plan_mats[data * 16 + parity];
+        if (cached.empty() && !rs_build_matrix(data, parity, cached))
+            return fail(nullptr, DM_ERR_INVALID, "singular Vandermonde top");
+        mat = cached;
+    }
+    RestorePlan p;
+    RC_TRY(restore_plan(nullptr, mat.data(), data, parity, present, in_place, p));
+    std::memcpy(inputs, p.inputs, sizeof(int) * (size_t)data);
+    std::memcpy(outputs, p.outputs, sizeof(int) * (size_t)p.nout);
+    std::memcpy(rows, p.rows, (size_t)p.nout * (size_t)data);
+    *nout = p.nout;
+    return DM_OK;
+}
+
+int dm_rs_restore_device_async(dm_rs* r, const void* const* dev_frags, uint64_t nseg, uint64_t segment, void* dev_obj,
+                               void* stream) {
+    if (!r) return bad_arg();
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    const int k = r->k, total = r->k + r->m;
+    if (!dev_frags || !dev_obj || nseg == 0 || segment == 0 || segment % (16ull * (uint64_t)k) || !is_aligned16(dev_obj))
+        return fail(c, DM_ERR_INVALID,
+                    "dm_rs_restore_device_async: need a 16-byte aligned object and a segment size that is a "
+                    "non-zero multiple of 16 x %d data shards", k);
+    for (uint64_t i = 0; i < nseg * (uint64_t)total; i++)
+        if (!is_aligned16(dev_frags[i]))
+            return fail(c, DM_ERR_INVALID, "dm_rs_restore_device_async: fragment %llu of segment %llu not 16-byte aligned",
+                        (unsigned long long)(i % total), (unsigned long long)(i / total));
+    const uint64_t frag = segment / (uint64_t)k;
+    RestoreBatch b;   // every plan first: a segment with too few fragments fails the call before any launch
+    b.desc.reserve(nseg);
+    for (uint64_t t = 0; t < nseg; t++)
+        RC_TRY(restore_add(r, b, reinterpret_cast<const uint8_t* const*>(dev_frags) + t * total,
+                           static_cast<uint8_t*>(dev_obj) + t * segment, frag));
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    return restore_launch(r, d, s, b, frag / 16);
+}
+
+int dm_restore_buffer(dm_rs* r, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
+                      const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, void* out,
+                      uint8_t* frag_status, uint8_t* seg_status, int* ok) {
+    if (!r || !ok) return bad_arg();
+    *ok = 0;
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    if (!frags || !out) return fail(c, DM_ERR_INVALID, "dm_restore_buffer: null argument");
+    RC_TRY(restore_check(r, nseg, size, segment));
+    std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
+    const int rc = restore_buffer(r, c->devs[g], frags, frag_names, seg_names, fid, nseg, size, segment, flags, out,
+                                  fst.data(), sst.data(), ok);
+    // no copy from the caller's memory stays queued, whichever way the call ends
+    if (rc != DM_OK || !*ok) (void)hipStreamSynchronize(c->devs[g].stream);
+    if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
+    if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
+    return rc;
+}
+
+int dm_retrieve_file(dm_rs* r, const char* fragdir, const uint8_t* frag_names, const uint8_t* seg_names,
+                     const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, const char* out_path,
+                     uint8_t* frag_status, uint8_t* seg_status, int* ok) {
+    if (!r || !ok) return bad_arg();
+    *ok = 0;
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    if (!fragdir || !frag_names || !out_path) return fail(c, DM_ERR_INVALID, "dm_retrieve_file: null argument");
+    RC_TRY(restore_check(r, nseg, size, segment));
+    std::string dir = fragdir;
+    while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
+    const std::string outp = out_path;
+    const size_t slash = outp.rfind('/');
+    const std::string tmp = (slash == std::string::npos ? std::string() : outp.substr(0, slash + 1)) + ".dm-rt-" +
+                            std::to_string((long long)::getpid()) + "-" +
+                            std::to_string((unsigned long long)g_rt_seq++);
+    FdGuard fd;
+    fd.fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd.fd < 0) return fail(c, DM_ERR_IO, "open %s: %s", outp.c_str(), go_errno(errno).c_str());   // as os.Create(out_path)
+    Dev& d = c->devs[g];
+    std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
+    int rc = retrieve_windows(r, d, dir, frag_names, seg_names, fid, nseg, size, segment, flags, fd.fd, tmp, fst.data(),
+                              sst.data(), ok);
+    if (rc != DM_OK) {   // a failed call may leave copies queued: none may land in a slot the next call fills
+        (void)hipStreamSynchronize(d.copy);
+        (void)hipStreamSynchronize(d.stream);
+    }
+    if (d.data.cap > kFpKeepBytes) c->reaper.put(d.id, d.data);
+    if (rs_ln(r, d).work.cap > kFpKeepBytes) c->reaper.put(d.id, rs_ln(r, d).work);
+    if (rc == DM_OK && *ok) {
+        if (::close(fd.fd) != 0) rc = fail(c, DM_ERR_IO, "close %s: %s", tmp.c_str(), go_errno(errno).c_str());
+        fd.fd = -1;
+        if (rc == DM_OK && ::rename(tmp.c_str(), outp.c_str()) != 0)
+            rc = fail(c, DM_ERR_IO, "rename %s %s: %s", tmp.c_str(), outp.c_str(), go_errno(errno).c_str());
+        if (rc != DM_OK) *ok = 0;
+    }
+    if (rc != DM_OK || !*ok) ::unlink(tmp.c_str());   // no temporary survives a failed call
+    if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
+    if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
+    return rc;
+}
+
+}  // extern "C"

@@ -66,6 +66,25 @@ bool gf_invert(const uint8_t* m, int k, uint8_t* out) {
     return true;
 }
 
+// klauspost buildMatrix: vandermonde(total, k) x inverse(top k x k), (k + m) x k row-major.
+bool rs_build_matrix(int k, int m, std::vector<uint8_t>& mat) {
+    const Gf& g = gf();
+    const int total = k + m;
+    std::vector<uint8_t> vm((size_t)total * k);
+    for (int i = 0; i < total; i++)
+        for (int j = 0; j < k; j++) vm[(size_t)i * k + j] = g.pow((uint8_t)i, j);
+    uint8_t inv[dm::kRsMaxIn * dm::kRsMaxIn];
+    if (!gf_invert(vm.data(), k, inv)) return false;
+    mat.assign((size_t)total * k, 0);
+    for (int i = 0; i < total; i++)
+        for (int j = 0; j < k; j++) {
+            uint8_t acc = 0;
+            for (int t = 0; t < k; t++) acc ^= g.mul(vm[(size_t)i * k + t], inv[t * k + j]);
+            mat[(size_t)i * k + j] = acc;
+        }
+    return true;
+}
+
 // Lookup table of `rows` (nout x k, row-major): entry [j][x] byte i = rows[i][j] * x.
 std::vector<uint64_t> rs_table(const uint8_t* rows, int nout, int k) {
     const Gf& g = gf();
@@ -88,6 +107,7 @@ namespace {
 struct RsLane {
     DevBuf dec_tab;             // per reconstruct call
     DevBuf work;                // host-API shard staging, process parity, FullProcessing windows
+    DevBuf rst_desc, rst_tab;   // restore: per-segment descriptors, coding tables (restore_capi.inl)
     PinnedBuf fp_slot[4];       // dm_full_processing: file / parity slots (fullproc_capi.inl)
 };
 
@@ -115,13 +135,17 @@ RsLane& rs_ln(dm_rs* r, const Dev& d) {
     return r->ln[(size_t)(&d - r->c->devs.data()) / (size_t)r->c->nphys];
 }
 
-void launch_rs(Dev& d, hipStream_t s, int k, const dm::RsArgs& a) {
-    const uint64_t units = a.units_per_seg;
+// Grid of the rs kernels: x strides over a segment's 16-byte units, y over segments.
+dim3 rs_grid(const Dev& d, uint64_t units, uint64_t nseg) {
     const uint64_t target = 8ull * (uint64_t)d.cus;   // workgroups in flight
-    const uint32_t gy = (uint32_t)std::min<uint64_t>({a.nseg, 65535ull, target});
+    const uint32_t gy = (uint32_t)std::min<uint64_t>({nseg, 65535ull, target});
     const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(units, dm::kRsThreads),
                                                                            ceil_div(target, gy)));
-    const dim3 grid(gx, gy), block(dm::kRsThreads);
+    return dim3(gx, gy);
+}
+
+void launch_rs(Dev& d, hipStream_t s, int k, const dm::RsArgs& a) {
+    const dim3 grid = rs_grid(d, a.units_per_seg, a.nseg), block(dm::kRsThreads);
     switch (k) {
         case 1: hipLaunchKernelGGL(dm::rs_code_kernel<1>, grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL(dm::rs_code_kernel<2>, grid, block, 0, s, a); break;
@@ -207,31 +231,18 @@ int dm_rs_create(dm_ctx* ctx, int data_shards, int parity_shards, dm_rs** out) {
     r->c = ctx;
     r->k = data_shards;
     r->m = parity_shards;
-    const int k = data_shards, total = data_shards + parity_shards;
-    // buildMatrix: vandermonde(total, k) x inverse(top k x k)
-    const Gf& g = gf();
-    std::vector<uint8_t> vm((size_t)total * k);
-    for (int i = 0; i < total; i++)
-        for (int j = 0; j < k; j++) vm[(size_t)i * k + j] = g.pow((uint8_t)i, j);
-    uint8_t inv[dm::kRsMaxIn * dm::kRsMaxIn];
-    if (!gf_invert(vm.data(), k, inv)) {
+    const int k = data_shards;
+    if (!rs_build_matrix(k, parity_shards, r->mat)) {
         delete r;
         return fail(c, DM_ERR_INVALID, "singular Vandermonde top");
     }
-    r->mat.assign((size_t)total * k, 0);
-    for (int i = 0; i < total; i++)
-        for (int j = 0; j < k; j++) {
-            uint8_t acc = 0;
-            for (int t = 0; t < k; t++) acc ^= g.mul(vm[(size_t)i * k + t], inv[t * k + j]);
-            r->mat[(size_t)i * k + j] = acc;
-        }
     const std::vector<uint64_t> tab = rs_table(r->mat.data() + (size_t)k * k, parity_shards, k);
     Dev& d = ctx->devs[0];
     r->ln.resize((size_t)ctx->lanes);
     r->enc_tab.rp = &ctx->reaper;
     r->enc_tab.dev = d.id;
     for (RsLane& L : r->ln)
-        for (DevBuf* b : {&L.dec_tab, &L.work}) {
+        for (DevBuf* b : {&L.dec_tab, &L.work, &L.rst_desc, &L.rst_tab}) {
             b->rp = &ctx->reaper;   // growth (work: FullProcessing windows) never synchronises the device
             b->dev = d.id;
         }
@@ -260,6 +271,8 @@ void dm_rs_destroy(dm_rs* r) {
         for (RsLane& L : r->ln) {
             L.dec_tab.release();
             L.work.release();
+            L.rst_desc.release();
+            L.rst_tab.release();
             for (auto& b : L.fp_slot) b.release();
         }
     }

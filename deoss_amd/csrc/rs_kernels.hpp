@@ -147,4 +147,104 @@ void rs_code_kernel(RsArgs a) {
     }
 }
 
+// ---- restore: many segments, each with its own erasure pattern, in one launch -----------------
+// The download side (cess-go-sdk process.Retrievefile: erasure.RSRestore per segment, join,
+// truncate).  Segment s has a descriptor: the k fragments it is rebuilt from, the data fragments
+// that are not yet at their final address in the object, and which coding table maps one to the
+// other (a missing fragment's row comes from the inverse sub-matrix, a fragment that is present
+// but lies elsewhere has a unit row: gather and decode are one pass).
+struct RsRestoreDesc {
+    const uint8_t* in[kRsMaxIn];   // the first k usable fragments, in index order
+    uint8_t* out[kRsMaxIn];        // final addresses of the data fragments to write (nout <= k)
+    uint32_t nout;                 // 0: every data fragment is in place, nothing to do
+    uint32_t table;                // index into RsRestoreArgs::tables
+};
+
+struct RsRestoreArgs {
+    const RsRestoreDesc* desc;     // [nseg]
+    const uint2* tables;           // [ntab][k][256] x 8 B, rs_code_kernel's layout
+    uint64_t units_per_seg;        // fragment bytes / 16
+    uint64_t nseg;
+};
+
+// Same grid and inner loop as rs_code_kernel.  The table lives in LDS and is reloaded only when the
+// next segment's table index differs (the index depends on seg alone, so every wave of the
+// workgroup takes the same branch and the barriers match).
+template <int NIN>
+__global__ __launch_bounds__(kRsThreads)
+void rs_restore_kernel(RsRestoreArgs a) {
+    __shared__ uint2 tab[NIN * 256];
+    uint32_t cur = 0xffffffffu;
+    const uint64_t ustride = (uint64_t)gridDim.x * kRsThreads;
+    for (uint64_t seg = blockIdx.y; seg < a.nseg; seg += gridDim.y) {
+        const RsRestoreDesc* ds = a.desc + seg;
+        const uint32_t nout = ds->nout;
+        if (nout == 0) continue;
+        const uint32_t ti = ds->table;
+        if (ti != cur) {
+            __syncthreads();   // every wave is done with the previous table
+            const uint2* src = a.tables + (uint64_t)ti * (NIN * 256);
+            for (uint32_t t = threadIdx.x; t < NIN * 256; t += kRsThreads) tab[t] = src[t];
+            __syncthreads();
+            cur = ti;
+        }
+        const uint8_t* in[NIN];
+#pragma unroll
+        for (int j = 0; j < NIN; j++) in[j] = ds->in[j];
+        uint8_t* out[NIN];   // entries past nout are never used
+#pragma unroll
+        for (int i = 0; i < NIN; i++) out[i] = ds->out[i];
+        uint64_t u = (uint64_t)blockIdx.x * kRsThreads + threadIdx.x;
+        // register double buffer: the next unit's loads are in flight while this one is coded
+        uint4 nx[NIN];
+        if (u < a.units_per_seg) {
+#pragma unroll
+            for (int j = 0; j < NIN; j++) nx[j] = rs_load(in[j] + u * 16);
+        }
+        for (; u < a.units_per_seg; u += ustride) {
+            const uint64_t off = u * 16;
+            uint4 x[NIN];
+#pragma unroll
+            for (int j = 0; j < NIN; j++) x[j] = nx[j];
+            if (u + ustride < a.units_per_seg) {
+#pragma unroll
+                for (int j = 0; j < NIN; j++) nx[j] = rs_load(in[j] + off + ustride * 16);
+            }
+            uint2 acc[16];
+#pragma unroll
+            for (int p = 0; p < 16; p++) acc[p] = make_uint2(0, 0);
+#pragma unroll
+            for (int j = 0; j < NIN; j++) {
+                const uint32_t w[4] = {x[j].x, x[j].y, x[j].z, x[j].w};
+                const uint2* tj = tab + j * 256;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint2 e = tj[(w[q] >> (8 * k)) & 0xffu];
+                        acc[4 * q + k].x ^= e.x;
+                        if (NIN > 4) acc[4 * q + k].y ^= e.y;   // nout <= NIN: the high half is unused
+                    }
+                }
+            }
+            uint32_t lo[4][4], hi[4][4];   // [q][row]
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                transpose4(acc[4 * q].x, acc[4 * q + 1].x, acc[4 * q + 2].x, acc[4 * q + 3].x, lo[q]);
+                if (NIN > 4) transpose4(acc[4 * q].y, acc[4 * q + 1].y, acc[4 * q + 2].y, acc[4 * q + 3].y, hi[q]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < NIN && i < (int)nout)
+                    rs_store(out[i] + off, make_uint4(lo[0][i], lo[1][i], lo[2][i], lo[3][i]));
+            if (NIN > 4) {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i + 4 < NIN && i + 4 < (int)nout)
+                        rs_store(out[i + 4] + off, make_uint4(hi[0][i], hi[1][i], hi[2][i], hi[3][i]));
+            }
+        }
+    }
+}
+
 }  // namespace dm

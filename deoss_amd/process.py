@@ -35,6 +35,7 @@ from .reedsolomon import DATA_SHARDS, PAR_SHARDS, Encoder
 
 SEGMENT_SIZE = 32 << 20                       # chain.SegmentSize
 FRAGMENT_SIZE = SEGMENT_SIZE // DATA_SHARDS   # chain.FragmentSize (8 MiB; node/tracker.go:250 "96M")
+RESTORE_VERIFY_FRAGMENTS, RESTORE_VERIFY_SEGMENTS, RESTORE_VERIFY_FID, RESTORE_VERIFY_ALL = 1, 2, 4, 7   # DM_RESTORE_*
 WINDOW_SEGMENTS = 8                           # segments per GPU call (256 MiB of file + 768 MiB of fragments; the Go shim bounds the segments in flight by DEOSS_PROCESS_MEM_GIB)
 
 
@@ -183,6 +184,76 @@ class Processor:
         if not found.value:
             return None
         return seg_i.value, frag_i.value, (out.raw if out is not None else None)
+
+    # -- restore (the download side) ---------------------------------------------------------------
+    def restore_buffer(self, frags, size: int, frag_names: Optional[bytes] = None,
+                       seg_names: Optional[bytes] = None, fid: Optional[bytes] = None,
+                       flags: int = RESTORE_VERIFY_ALL, out=None) -> Tuple[bool, Optional[bytes], bytes, bytes]:
+        """``dm_restore_buffer``: the object from fragments in memory.  ``frags``: nseg x (data +
+        parity) fragments, flat or one list per segment, ``None`` = not downloaded.  Returns (ok,
+        the object's ``size`` bytes or None, fragment statuses, segment statuses); a failed check is
+        ``ok = False``, not an exception.  ``out``: a ctypes buffer of ``size`` bytes to fill instead
+        (left untouched unless ok)."""
+        total = self.k + self.m
+        flat = [f for seg in frags for f in seg] if frags and isinstance(frags[0], (list, tuple)) else list(frags)
+        if len(flat) % total:
+            raise DeossMerkleError(DM_ERR_INVALID, "need data + parity entries per segment")
+        nseg = len(flat) // total
+        keep = [ctypes.create_string_buffer(bytes(f), len(f)) if f is not None else None for f in flat]
+        for b in keep:
+            if b is not None and len(b) != self.frag:
+                raise DeossMerkleError(DM_ERR_INVALID, "fragment sizes do not match")
+        ptrs = (ctypes.c_void_p * max(len(flat), 1))(*[ctypes.addressof(b) if b is not None else None for b in keep])
+        dst = out if out is not None else ctypes.create_string_buffer(max(size, 1))
+        fst = ctypes.create_string_buffer(max(nseg * total, 1))
+        sst = ctypes.create_string_buffer(max(nseg, 1))
+        ok = ctypes.c_int(0)
+        self._check(self.ctx._L.dm_restore_buffer(self.enc._h, ptrs, frag_names, seg_names, fid, nseg, size,
+                                                  self.segment, flags, dst, fst, sst, ctypes.byref(ok)),
+                    "dm_restore_buffer")
+        data = dst.raw[:size] if (ok.value and out is None) else None
+        return bool(ok.value), data, fst.raw[:nseg * total], sst.raw[:nseg]
+
+    def retrieve_file(self, fragdir: str, frag_names: bytes, size: int, out_path: str,
+                      seg_names: Optional[bytes] = None, fid: Optional[bytes] = None,
+                      flags: int = RESTORE_VERIFY_ALL) -> Tuple[bool, bytes, bytes]:
+        """``dm_retrieve_file``: the object from the fragment files ``fragdir/<hex name>`` into
+        ``out_path`` (written only when everything asked for held).  Returns (ok, fragment statuses,
+        segment statuses)."""
+        total = self.k + self.m
+        nseg = len(frag_names) // (32 * total)
+        fst = ctypes.create_string_buffer(max(nseg * total, 1))
+        sst = ctypes.create_string_buffer(max(nseg, 1))
+        ok = ctypes.c_int(0)
+        L = self.ctx._L
+        rc = L.dm_retrieve_file(self.enc._h, os.fsencode(fragdir), frag_names, seg_names, fid, nseg, size,
+                                self.segment, flags, os.fsencode(out_path), fst, sst, ctypes.byref(ok))
+        if rc == DM_ERR_IO:   # file errors keep Go's text
+            raise DeossMerkleError(rc, (L.dm_last_error(None) or b"").decode())
+        self._check(rc, "dm_retrieve_file")
+        return bool(ok.value), fst.raw[:nseg * total], sst.raw[:nseg]
+
+    def RestoreFile(self, fragdir: str, segments: List[SegmentDataInfo], size: int, out_path: str
+                    ) -> Tuple[bool, Optional[Exception]]:
+        """The RSRestore / join / truncate part of process.Retrievefile: ``segments`` is what
+        FullProcessing returned (names = base names of its paths), the fragments are whichever of
+        them lie in ``fragdir``.  Every fragment used and every restored segment is checked against
+        its name.  (True, None), or (False, error)."""
+        total = self.k + self.m
+        try:
+            segn = b"".join(bytes.fromhex(os.path.basename(s.SegmentHash)) for s in segments)
+            fragn = b"".join(bytes.fromhex(os.path.basename(f)) for s in segments for f in s.FragmentHash)
+            if len(segn) != 32 * len(segments) or len(fragn) != 32 * total * len(segments):
+                raise ValueError("segment and fragment names must be hex SHA-256")
+            ok, fst, sst = self.retrieve_file(fragdir, fragn, size, out_path, seg_names=segn,
+                                              flags=RESTORE_VERIFY_FRAGMENTS | RESTORE_VERIFY_SEGMENTS)
+        except (OSError, ValueError, DeossMerkleError) as e:
+            return False, e
+        if not ok:
+            bad = [s for s in range(len(sst)) if sst[s]]
+            return False, DeossMerkleError(DM_ERR_INVALID, "restore failed: segment(s) %s could not be rebuilt "
+                                           "from verified fragments" % ", ".join(map(str, bad)))
+        return True, None
 
     def FullProcessing(self, file: str, cipher: str, savedir: str
                        ) -> Tuple[Optional[List[SegmentDataInfo]], str, Optional[Exception]]:
@@ -362,6 +433,18 @@ def FullProcessing(file: str, cipher: str, savedir: str
         except DeossMerkleError as e:   # no GPU: the Go shape (nil, "", err), as gpu() fails in Go
             return None, "", e
     return _default.FullProcessing(file, cipher, savedir)
+
+
+def RestoreFile(fragdir: str, segments: List[SegmentDataInfo], size: int, out_path: str
+                ) -> Tuple[bool, Optional[Exception]]:
+    """The restore part of process.Retrievefile on the default GPU pipeline (Processor.RestoreFile)."""
+    global _default
+    if _default is None:
+        try:
+            _default = Processor()
+        except DeossMerkleError as e:   # no GPU: fails the Go way, as FullProcessing
+            return False, e
+    return _default.RestoreFile(fragdir, segments, size, out_path)
 
 
 def FindFragment(fpath: str, fragment_hash: str) -> Tuple[Optional[bytes], Optional[Exception]]:

@@ -148,6 +148,45 @@ class Encoder:
                     "dm_rs_reconstruct_device_async")
 
 
+    def restore_device_async(self, frag_ptrs: Sequence[int], nseg: int, segment: int, obj_ptr: int,
+                             stream: int = 0) -> None:
+        """``dm_rs_restore_device_async``: ``nseg`` segments, each with its own erasure pattern, in one
+        kernel launch.  ``frag_ptrs``: nseg x total device addresses (0 / None = absent); afterwards
+        ``obj_ptr`` holds every segment's data fragments in order."""
+        n = nseg * self.total_shards
+        if len(frag_ptrs) != n:
+            raise DeossMerkleError(-2, "need one pointer per fragment of every segment")
+        ptrs = (ctypes.c_void_p * n)(*[p or None for p in frag_ptrs])
+        self._check(self._L.dm_rs_restore_device_async(self._h, ptrs, nseg, segment, obj_ptr, stream),
+                    "dm_rs_restore_device_async")
+
+
+def restore_plan(present: Sequence[bool], in_place: Optional[Sequence[bool]] = None,
+                 data_shards: int = DATA_SHARDS, parity_shards: int = PAR_SHARDS
+                 ) -> Tuple[List[int], List[int], List[List[int]]]:
+    """``dm_rs_restore_plan`` (pure host function, no GPU): for one erasure pattern the fragments
+    read (the first ``data_shards`` present in index order), the data fragments written (missing
+    or not ``in_place``) and one coding row per output.  Raises :class:`ErrTooFewShards`."""
+    from ._lib import load_library
+    L = load_library()
+    k, t = data_shards, data_shards + parity_shards
+    if len(present) != t or (in_place is not None and len(in_place) != k):
+        raise DeossMerkleError(-2, "present needs data + parity entries, in_place data entries")
+    ins, outs = (ctypes.c_int * k)(), (ctypes.c_int * k)()
+    rows = ctypes.create_string_buffer(k * k)
+    nout = ctypes.c_int()
+    pres = bytes(int(bool(p)) for p in present)
+    inp = bytes(int(bool(p)) for p in in_place) if in_place is not None else None
+    rc = L.dm_rs_restore_plan(k, parity_shards, pres, inp, ins, outs, rows, ctypes.byref(nout))
+    if rc != 0:
+        detail = (L.dm_last_error(None) or b"").decode()
+        if "too few shards" in detail:
+            raise ErrTooFewShards(rc, detail)
+        raise DeossMerkleError(rc, detail)
+    n = nout.value
+    return list(ins), list(outs[:n]), [list(rows.raw[i * k:(i + 1) * k]) for i in range(n)]
+
+
 def New(ctx: MerkleContext, data_shards: int = DATA_SHARDS, parity_shards: int = PAR_SHARDS) -> Encoder:
     """reedsolomon.New(dataShards, parityShards) on the context's first GPU."""
     return Encoder(ctx, data_shards, parity_shards)

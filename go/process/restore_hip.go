@@ -1,0 +1,163 @@
+//go:build hip
+
+// Restore: the download side of the package.  cess-go-sdk process.Retrievefile(chainer, fmeta, fid,
+// dir, cipher) (called at node/fileHandler.go:519, :600 and :990) fetches, per segment, any
+// chain.DataShards of its fragments from miners, rebuilds the missing data fragments
+// (erasure.RSRestore), joins the segments and cuts the zero padding off at the file size.  The SDK
+// goes on fetching; RestoreFile / RestoreFragments replace the rest with one GPU pass that also
+// checks every fragment it uses against its name (its SHA-256) -- falling back to another fragment
+// when one fails -- and every rebuilt segment against the segment name (include/deoss_merkle.h:
+// dm_retrieve_file, dm_restore_buffer).  Downloads with cipher != "" stay with the SDK.
+package process
+
+/*
+#cgo pkg-config: deoss_merkle
+#include <stdlib.h>
+#include "deoss_merkle.h"
+*/
+import "C"
+
+import (
+	"encoding/hex"
+	"errors"
+	"fmt"
+	"path/filepath"
+	"runtime"
+	"unsafe"
+
+	"github.com/CESSProject/cess-go-sdk/chain"
+)
+
+// ErrRestore: the fragments at hand do not give the object back (too few verified fragments of
+// some segment, or a rebuilt segment that is not the one its name promises).
+var ErrRestore = errors.New("restore: too few verified fragments or a segment mismatch")
+
+// names decodes the base names of FullProcessing's paths (hex SHA-256) into digests.
+func names(segs []chain.SegmentDataInfo) (segn, fragn []byte, err error) {
+	total := chain.DataShards + chain.ParShards
+	segn = make([]byte, 0, 32*len(segs))
+	fragn = make([]byte, 0, 32*len(segs)*total)
+	for _, s := range segs {
+		if len(s.FragmentHash) != total {
+			return nil, nil, fmt.Errorf("restore: segment with %d fragment names, want %d", len(s.FragmentHash), total)
+		}
+		d, e := hex.DecodeString(filepath.Base(s.SegmentHash))
+		if e != nil || len(d) != 32 {
+			return nil, nil, errors.New("restore: segment name is not a hex SHA-256")
+		}
+		segn = append(segn, d...)
+		for _, f := range s.FragmentHash {
+			d, e := hex.DecodeString(filepath.Base(f))
+			if e != nil || len(d) != 32 {
+				return nil, nil, errors.New("restore: fragment name is not a hex SHA-256")
+			}
+			fragn = append(fragn, d...)
+		}
+	}
+	return segn, fragn, nil
+}
+
+// restoreError must run on the OS thread that made the call (dm_last_error is thread-local).
+func restoreError(rc C.int) error {
+	if rc == C.DM_ERR_EMPTY {
+		return errors.New("Empty data")
+	}
+	if msg := C.GoString(C.dm_last_error(nil)); msg != "" {
+		return errors.New(msg)
+	}
+	return errors.New(C.GoString(C.dm_strerror(rc)))
+}
+
+// RestoreFile rebuilds the file of size bytes at outPath from whichever fragments of segs (what
+// FullProcessing returned, or the same names taken from the chain's file metadata) lie in
+// fragDir/<name>.  Per segment the first chain.DataShards fragment files that exist are read;
+// further ones only when one fails its check.  outPath appears only when every segment held.
+func RestoreFile(fragDir string, segs []chain.SegmentDataInfo, size uint64, outPath string) error {
+	if err := gpu(); err != nil {
+		return err
+	}
+	if len(segs) == 0 {
+		return errors.New("Empty data")
+	}
+	segn, fragn, err := names(segs)
+	if err != nil {
+		return err
+	}
+	rs := <-pipes
+	defer func() { pipes <- rs }()
+	cdir, cout := C.CString(fragDir), C.CString(outPath)
+	defer C.free(unsafe.Pointer(cdir))
+	defer C.free(unsafe.Pointer(cout))
+	var ok C.int
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	rc := C.dm_retrieve_file(rs, cdir, (*C.uint8_t)(unsafe.Pointer(&fragn[0])), (*C.uint8_t)(unsafe.Pointer(&segn[0])), nil,
+		C.uint64_t(len(segs)), C.uint64_t(size), C.uint64_t(chain.SegmentSize),
+		C.int(C.DM_RESTORE_VERIFY_FRAGMENTS|C.DM_RESTORE_VERIFY_SEGMENTS), cout, nil, nil, &ok)
+	if rc != C.DM_OK {
+		return restoreError(rc)
+	}
+	if ok == 0 {
+		return ErrRestore
+	}
+	return nil
+}
+
+// RestoreFragments is RestoreFile for bytes already in memory: frags[s][j] is fragment j of segment
+// s (data fragments first) or nil when it was not fetched.  Returns the file's size bytes.
+func RestoreFragments(frags [][][]byte, segs []chain.SegmentDataInfo, size uint64) ([]byte, error) {
+	if err := gpu(); err != nil {
+		return nil, err
+	}
+	total := chain.DataShards + chain.ParShards
+	frag := int(chain.SegmentSize) / chain.DataShards
+	if len(segs) == 0 || len(frags) != len(segs) || size == 0 {
+		return nil, errors.New("Empty data")
+	}
+	segn, fragn, err := names(segs)
+	if err != nil {
+		return nil, err
+	}
+	// the pointer table lives in C memory (cgo forbids Go pointers to Go pointers); the fragments
+	// themselves are pinned for the call
+	n := len(segs) * total
+	table := (*[1 << 28]unsafe.Pointer)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if table == nil {
+		return nil, errors.New("restore: out of memory")
+	}
+	defer C.free(unsafe.Pointer(table))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for s := range frags {
+		if len(frags[s]) != total {
+			return nil, fmt.Errorf("restore: segment %d has %d fragment slots, want %d", s, len(frags[s]), total)
+		}
+		for j, f := range frags[s] {
+			if f == nil {
+				continue
+			}
+			if len(f) != frag {
+				return nil, fmt.Errorf("restore: fragment %d of segment %d has %d bytes, want %d", j, s, len(f), frag)
+			}
+			pin.Pin(&f[0])
+			table[s*total+j] = unsafe.Pointer(&f[0])
+		}
+	}
+	out := make([]byte, size)
+	rs := <-pipes
+	defer func() { pipes <- rs }()
+	var ok C.int
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	rc := C.dm_restore_buffer(rs, (*unsafe.Pointer)(unsafe.Pointer(table)), (*C.uint8_t)(unsafe.Pointer(&fragn[0])),
+		(*C.uint8_t)(unsafe.Pointer(&segn[0])), nil, C.uint64_t(len(segs)), C.uint64_t(size),
+		C.uint64_t(chain.SegmentSize), C.int(C.DM_RESTORE_VERIFY_FRAGMENTS|C.DM_RESTORE_VERIFY_SEGMENTS),
+		unsafe.Pointer(&out[0]), nil, nil, &ok)
+	if rc != C.DM_OK {
+		return nil, restoreError(rc)
+	}
+	if ok == 0 {
+		return nil, ErrRestore
+	}
+	return out, nil
+}

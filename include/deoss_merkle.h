@@ -273,6 +273,61 @@ int dm_full_processing(dm_rs *rs, const char *path, const char *savedir, uint64_
 int dm_fragment_lookup(dm_rs *rs, const char *path, uint64_t segment, const uint8_t want[32], void *out,
                        uint64_t out_cap, int *found, uint64_t *seg_idx, int *frag_idx);
 
+/* ---- restore: the download side (cess-go-sdk process.Retrievefile, node/fileHandler.go:519,600,990)
+ * Any `data` of a segment's data + parity fragments rebuild its data fragments (erasure.RSRestore);
+ * the segments joined and cut at the file size are the object.
+ *
+ * dm_rs_restore_plan: the plan of one erasure pattern (pure host function: no GPU, no context; the
+ * runtime uses this same rule).  present[data + parity]: 1 = usable; in_place[data] (nullable =
+ * none): 1 = that data fragment already lies at its final address.  inputs[data]: the fragments
+ * read, the first `data` present ones in index order (klauspost's rule); outputs[*nout]: the data
+ * fragments written, every one that is missing or not in place (room for `data`); rows: *nout x data
+ * coding rows (room for data x data), output i = sum_j rows[i][j] * inputs[j] over GF(2^8).  Fewer
+ * than `data` present: DM_ERR_INVALID "too few shards given (%d of %d needed)". */
+int dm_rs_restore_plan(int data, int parity, const uint8_t *present, const uint8_t *in_place, int *inputs,
+                       int *outputs, uint8_t *rows, int *nout);
+/* Many segments, each with its own erasure pattern, in ONE kernel launch on `stream`.  dev_frags:
+ * host array of nseg x (data + parity) device pointers (16-byte aligned; NULL = absent; a fragment
+ * may overlap [dev_obj, dev_obj + nseg*segment) only by being data fragment j of segment s at
+ * dev_obj + s*segment + j*(segment/data), which is then left as it is).  On return, in stream
+ * order, dev_obj (16-byte aligned) holds every segment's data fragments in order.  segment: a
+ * multiple of 16 x data.  No verification.  A segment with too few fragments fails the whole call
+ * (DM_ERR_INVALID "too few shards given ...") before anything is launched. */
+int dm_rs_restore_device_async(dm_rs *rs, const void *const *dev_frags, uint64_t nseg, uint64_t segment,
+                               void *dev_obj, void *stream);
+/* Verification asked of dm_restore_buffer / dm_retrieve_file (flags, or-ed). */
+#define DM_RESTORE_VERIFY_FRAGMENTS 1   /* every fragment used: SHA-256 == its name (frag_names) */
+#define DM_RESTORE_VERIFY_SEGMENTS 2    /* every restored, zero-padded segment: SHA-256 == seg_names */
+#define DM_RESTORE_VERIFY_FID 4         /* hashtree root over the segment digests == fid */
+#define DM_RESTORE_VERIFY_ALL 7
+/* Restore an object from fragments in host memory (synchronous, one call lane).  frags: nseg x
+ * (data + parity) host pointers to segment/data bytes each, NULL = not downloaded.  frag_names
+ * (nseg x (data + parity) x 32), seg_names (nseg x 32), fid (32): the SHA-256 names, each nullable
+ * (its check is then skipped, as without its flag).  With DM_RESTORE_VERIFY_FRAGMENTS every supplied
+ * fragment is hashed in one leaf launch; one that does not match its name is bad, is treated as
+ * absent, and the next good fragment in index order takes its place.  One restore launch, then
+ * the segment and fid checks.  `size` bytes ((nseg-1)*segment < size <= nseg*segment; the padding
+ * beyond is covered by the segment digests and never copied) are written to `out` ONLY when
+ * everything asked for held: *ok = 1; otherwise `out` is untouched and *ok = 0 -- a result, not an
+ * error (DM_OK).  With flags = 0 the fragments are used as given.
+ * frag_status[s*(data+parity)+j] (nullable): 0 absent (dm_retrieve_file: or never looked at), 1 used,
+ * 2 good but not needed (every good fragment of a segment that has too few), 3 bad.
+ * seg_status[s] (nullable): 0 ok, 1 too few good fragments, 2 segment digest mismatch.
+ * nseg == 0: DM_ERR_EMPTY. */
+int dm_restore_buffer(dm_rs *rs, const void *const *frags, const uint8_t *frag_names, const uint8_t *seg_names,
+                      const uint8_t *fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, void *out,
+                      uint8_t *frag_status, uint8_t *seg_status, int *ok);
+/* The same from fragment files fragdir/<lower-case hex name> (the layout dm_full_processing writes;
+ * frag_names is required).  A file that does not exist is absent; one of the wrong length is bad.
+ * Per segment the first `data` fragment files that exist are read, further ones only when a check
+ * fails.  Works in windows of segments through pinned slots (device and pinned memory do not grow
+ * with the object).  The output is written under a temporary name next to out_path and renamed to
+ * out_path only when *ok = 1; no temporary file is left behind otherwise.  I/O errors keep Go's
+ * texts ("open <path>: permission denied"). */
+int dm_retrieve_file(dm_rs *rs, const char *fragdir, const uint8_t *frag_names, const uint8_t *seg_names,
+                     const uint8_t *fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
+                     const char *out_path, uint8_t *frag_status, uint8_t *seg_status, int *ok);
+
 /* FullProcessing while the upload body arrives (SURVEY.md 8f #1 + #2): the handlers write the body
  * to a file (node/objectHandler.go:248-266, node/fileHandler.go:899-937) and then run
  * FullProcessing(fpath, "", cacheDir) over it (node/objectHandler.go:168, node/fileHandler.go:771).

@@ -159,6 +159,43 @@ inline std::pair<std::vector<uint8_t>, std::optional<Error>> FindFragment(const 
     return {std::move(out), std::nullopt};
 }
 
+// RestoreFile(fragDir, segs, size, outPath) (go/process/restore_hip.go): the RSRestore / join /
+// truncate part of process.Retrievefile (node/fileHandler.go:519,600,990).  segs is what
+// FullProcessing returned; whichever of its fragments lie in fragDir/<name> rebuild the file of
+// `size` bytes at outPath.  dm_retrieve_file: every fragment used and every restored segment is
+// checked against its name; outPath appears only when all held.
+inline std::optional<Error> RestoreFile(const std::string& fragdir, const std::vector<SegmentDataInfo>& segs,
+                                        uint64_t size, const std::string& out_path) {
+    auto base32 = [](const std::string& path, uint8_t* out) -> bool {
+        const std::string n = path.substr(path.rfind('/') == std::string::npos ? 0 : path.rfind('/') + 1);
+        auto nib = [](char ch) -> int { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : -1; };
+        if (n.size() != 64) return false;
+        for (int i = 0; i < 32; i++) {
+            const int hi = nib(n[2 * i]), lo = nib(n[2 * i + 1]);
+            if (hi < 0 || lo < 0) return false;
+            out[i] = (uint8_t)(hi * 16 + lo);
+        }
+        return true;
+    };
+    const int total = DataShards + ParShards;
+    std::vector<uint8_t> segn(32 * segs.size()), fragn(32 * segs.size() * total), sst(segs.size());
+    for (size_t s = 0; s < segs.size(); s++) {
+        bool ok = (int)segs[s].FragmentHash.size() == total && base32(segs[s].SegmentHash, segn.data() + 32 * s);
+        for (int j = 0; ok && j < total; j++) ok = base32(segs[s].FragmentHash[j], fragn.data() + 32 * (s * total + j));
+        if (!ok) return Error{DM_ERR_INVALID, "process: segment and fragment names must be hex SHA-256"};
+    }
+    auto& p = Pipelines::instance();
+    dm_rs* rs = p.pick();
+    if (!rs) return Error{p.status(), dm_strerror(p.status())};
+    int ok = 0;
+    const int rc = dm_retrieve_file(rs, fragdir.c_str(), fragn.data(), segn.data(), nullptr, segs.size(), size, SegmentSize,
+                                    DM_RESTORE_VERIFY_FRAGMENTS | DM_RESTORE_VERIFY_SEGMENTS, out_path.c_str(), nullptr,
+                                    sst.data(), &ok);
+    if (rc != DM_OK) return last_error(rc);
+    if (!ok) return Error{DM_ERR_INVALID, "process: restore failed: too few verified fragments or a segment mismatch"};
+    return std::nullopt;
+}
+
 // FullProcessing while the body arrives (dm_pstream_*): Write the pieces, then Close.
 class Writer {
   public:
