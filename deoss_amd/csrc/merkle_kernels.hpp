@@ -254,6 +254,22 @@ __device__ __forceinline__ void leaf_epilogue(const LeafArgs& a, uint64_t i, con
     }
 }
 
+// Smallest value over the 64 lanes of the wave.
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t y = __shfl_xor(x, o, 64);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+// a wave-uniform value as a scalar (loop counters and bounds then stay on the SALU)
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t x) {
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32) |
+           __builtin_amdgcn_readfirstlane((uint32_t)x);
+}
+
 // Largest value over the 64 lanes of the wave (wave-uniform result).
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t x) {
 #pragma unroll
@@ -570,7 +586,8 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_pair(LeafArgs a) {
 //   F  = bitop3 pair of K1P                 Ch(e,f,g) / Maj(a,b,c)
 //   X7 = S + F + H                          e(s+1) / a(s-1)
 //   HN = (X6 ^ N) + V + X4[lane ^ 8]        next H: h + KW + d / T1 = e - d   (N = 0 / ~0, V = KW / 1)
-// 8 instructions per step, a 4-deep chain (alignbit, xor, xor, add3); 66 steps per 64-byte block.
+// 8 instructions per step, a 4-deep chain (alignbit, xor, xor, add3); 66 steps per 64-byte block
+// on its own, 64 where blocks are linked into one stream (the register path, DM_QS_LINKQ).
 // The earlier lock-step form (both triples on one round, two bank-masked exchanges) took 9
 // instructions and a 5-deep chain: 669.9 -> 625.7 ms for the 8 GiB / 32 MiB headline.  The
 // producer wave gives each of a leaf's 8 lanes its own block (8 consecutive blocks per ring
@@ -605,28 +622,12 @@ static_assert(4 * kQuadLdsBytes <= (160u << 10), "four compact K1Q workgroups mu
 // half-rate slot).  hipcc re-associates DPP xors and cannot emit bank-masked DPP ops, so the
 // steps are written out.  Wait states: every DPP source VGPR is written at least two
 // instructions earlier.
-#ifndef DM_QS_DEEP3
-#define DM_QS_DEEP3 0
-#endif
-#if DM_QS_DEEP3
-// Experiment ("3-deep e-chain"; A/B only, tools/deep3_ab.sh): every lane of a triple
-// makes all three rotations itself (sh / sh2 / sh3 = 6,11,25 or 2,13,22) and one xor3 gives Sigma,
-// so the chain is alignbit -> xor3 -> add3 (3 deep) at 9 instructions per step instead of 8.
-#define DM_QS_HEAD(X4, X5, X6)                                                                   \
-    "v_alignbit_b32 %[r], %[" X4 "], %[" X4 "], %[sh]\n\t"                                      \
-    "v_alignbit_b32 %[s], %[" X4 "], %[" X4 "], %[sh2]\n\t"                                     \
-    "v_alignbit_b32 %[t], %[" X4 "], %[" X4 "], %[sh3]\n\t"                                     \
-    "v_bitop3_b32 %[f], %[" X4 "], %[" X5 "], %[msk] bitop3:0x1e\n\t"                          \
-    "v_bitop3_b32 %[f], %[f], %[" X6 "], %[" X5 "] bitop3:0xca\n\t"
-#define DM_QS_SIGMA "v_bitop3_b32 %[s], %[r], %[s], %[t] bitop3:0x96\n\t"
-#else
 #define DM_QS_HEAD(X4, X5, X6)                                                                   \
     "v_alignbit_b32 %[r], %[" X4 "], %[" X4 "], %[sh]\n\t"                                      \
     "v_bitop3_b32 %[f], %[" X4 "], %[" X5 "], %[msk] bitop3:0x1e\n\t"                          \
     "v_bitop3_b32 %[f], %[f], %[" X6 "], %[" X5 "] bitop3:0xca\n\t"                             \
     "v_xor_b32_dpp %[s], %[r], %[r] quad_perm:[1,2,0,3] row_mask:0xf bank_mask:0xf\n\t"
 #define DM_QS_SIGMA "v_xor_b32_dpp %[s], %[r], %[s] quad_perm:[2,0,1,3] row_mask:0xf bank_mask:0xf\n\t"
-#endif
 // VN's round comes from lane QP of the quad (QP = "[0,1,2,3]": every lane holds it, the generic
 // path; "[j,j,j,j]": the register path's lane j holds it, see quad_block_regs)
 #define DM_QS_STEP_Q(X4, X5, X6, X7, H, HN, VN, QP)                                             \
@@ -659,10 +660,19 @@ static_assert(4 * kQuadLdsBytes <= (160u << 10), "four compact K1Q workgroups mu
 // drops to 12.85 and the compact one rises to 368 (reproducible over every odd and even shift,
 // profiles/r01/r01f_align_ab.log).  So each step stream is pinned: 8-byte aligned, plus one 4-byte
 // s_nop for the compact kernel (MIS).  Cause not isolated (instruction fetch / issue arbitration
-// between the two waves sharing a SIMD in the compact case).
-#define DM_QS_ALIGN ".p2align 3\n\t"
+// between the two waves sharing a SIMD in the compact case).  Measured again with the linked
+// stream (8 x 64 + 2 steps per stage; profiles/k1q_overlap/): wide 479.3 ms per 8 GiB step at
+// 0 mod 8 and 595.8 at 4 mod 8; compact (8,192 x 1 MiB) 18.95 ms at 4 mod 8 and 26.0 at 0 mod 8.
+// The pins stay.  The per-block path (quad_block_skewed) takes its kernel's pin too: in the
+// compact kernel it sits at 4 mod 8, where it was at 0.  That is for the placement guard, not for
+// speed: tests/test_code_placement.py wants 1,056 step v_xor_b32_dpp at the pin (8 x 66 x 2, the old
+// register path alone), the linked stream has 1,028, and the per-block path's 132 make up the
+// rest.  Cost: +1.1 % on a compact launch that runs this path alone (8,192 leaves of 7 blocks:
+// 70.5 -> 71.3 us), nothing measurable behind whole stages (15 blocks 84.1 -> 84.1, 23 blocks
+// 92.6 -> 92.4 us; profiles/k1q_overlap/README.md).  With the guard's count at 1,028 this path
+// can return to 0 mod 8.
 #define DM_QS_ALIGN_MIS ".p2align 3\n\t.if %[mis]\n\ts_nop 0\n\t.endif\n\t"
-#define DM_QS_PROLOGUE(V) DM_QS_PROLOGUE_AT(V, DM_QS_ALIGN, "[0,1,2,3]")
+#define DM_QS_PROLOGUE(V) DM_QS_PROLOGUE_AT(V, DM_QS_ALIGN_MIS, "[0,1,2,3]")
 // H of step 0, as if made by step -1 (X6 = P3, X4 = P1); P may have just been copied from x
 #define DM_QS_PROLOGUE_AT(V, ALIGN, QP)                                                           \
     "s_nop 1\n\t" ALIGN                                                                          \
@@ -703,27 +713,19 @@ static_assert(4 * kQuadLdsBytes <= (160u << 10), "four compact K1Q workgroups mu
     DM_QS_STEP_A("a", "b", "c", "d", "h", "g") DM_QS_STEP_END("d", "a", "b", "c", "g")           \
     DM_QS_FF("x0", "a", "0xc") DM_QS_FF("x1", "b", "0xc") DM_QS_FF("x3", "d", "0xc")             \
     DM_QS_FF("x2", "c", "0xc")
-#if DM_QS_DEEP3
-#define DM_QS_XOUT , [t] "=&v"(t_)
-#define DM_QS_XIN , [sh2] "v"(sh.y), [sh3] "v"(sh.z)
-#else
-#define DM_QS_XOUT
-#define DM_QS_XIN
-#endif
 #define DM_QS_OUT                                                                                \
     : [a] "+v"(p0), [b] "+v"(p1), [c] "+v"(p2), [d] "+v"(p3), [h] "+v"(h), [g] "+v"(g),           \
       [x0] "+v"(x[0]), [x1] "+v"(x[1]), [x2] "+v"(x[2]), [x3] "+v"(x[3]), [r] "=&v"(r_),          \
-      [f] "=&v"(f_), [s] "=&v"(s_) DM_QS_XOUT
-#define DM_QS_OPS DM_QS_OUT : [sh] "v"(sh.x), [msk] "v"(msk), [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [v3] "v"(v3) DM_QS_XIN
+      [f] "=&v"(f_), [s] "=&v"(s_)
+#define DM_QS_OPS DM_QS_OUT : [mis] "i"(MIS ? 1 : 0), [sh] "v"(sh.x), [msk] "v"(msk), [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [v3] "v"(v3)
 
 // One 64-byte block from the ring: 66 skewed steps (the a-triple starts two steps late and
 // finishes two steps after the e-triple).  x = this lane's chaining words: e-triple (e,f,g,h),
 // a-triple (c,d,a,b) -- stored rotated so that both triples start from P = x and feed forward
 // x += P.  kw(grp) gives -(K+W) of rounds 4grp..4grp+3 (an LDS read).
-template <class KW>
+template <bool MIS, class KW>
 __device__ __forceinline__ void quad_block_skewed(uint32_t (&x)[4], KW kw, uint3 sh, uint32_t msk) {
-    uint32_t p0 = x[0], p1 = x[1], p2 = x[2], p3 = x[3], h = 0, g = 0, r_, f_, s_, t_;
-    (void)t_;
+    uint32_t p0 = x[0], p1 = x[1], p2 = x[2], p3 = x[3], h = 0, g = 0, r_, f_, s_;
     uint4 q = kw(0), nq = kw(1);
     {
         const uint32_t v0 = q.x, v1 = 0, v2 = 0, v3 = 0;
@@ -735,11 +737,11 @@ __device__ __forceinline__ void quad_block_skewed(uint32_t (&x)[4], KW kw, uint3
         const uint4 nnq = grp + 2 < 16 ? kw(grp + 2) : nq;
         const uint32_t v0 = q.y, v1 = q.z, v2 = q.w, v3 = nq.x;
         if (grp == 0) {
-            asm volatile(DM_QS_ALIGN DM_QS_GROUP0("v0", "v1", "v2", "v3") DM_QS_OPS);
+            asm volatile(DM_QS_ALIGN_MIS DM_QS_GROUP0("v0", "v1", "v2", "v3") DM_QS_OPS);
         } else if (grp < 15) {
-            asm volatile(DM_QS_ALIGN DM_QS_STEPS4V("v0", "v1", "v2", "v3") DM_QS_OPS);
+            asm volatile(DM_QS_ALIGN_MIS DM_QS_STEPS4V("v0", "v1", "v2", "v3") DM_QS_OPS);
         } else {
-            asm volatile(DM_QS_ALIGN DM_QS_TAIL("v0", "v1", "v2") DM_QS_OPS);
+            asm volatile(DM_QS_ALIGN_MIS DM_QS_TAIL("v0", "v1", "v2") DM_QS_OPS);
         }
         q = nq;
         nq = nnq;
@@ -748,65 +750,137 @@ __device__ __forceinline__ void quad_block_skewed(uint32_t (&x)[4], KW kw, uint3
 
 constexpr int kLgkmWait0 = 0xC07F;   // s_waitcnt lgkmcnt(0), no wait on vmcnt / expcnt (gfx9 encoding)
 
-// quad_block_skewed with the block's 64 words of -(K+W) in registers: the whole block is one asm
-// statement (hipcc puts an s_nop between asm statements that share registers).  The 64 words are
-// spread over the 4 lanes of a quad: lane j's K[t] holds rounds 16t + 4j .. 16t + 4j + 3, and
-// round r's step reads its word from quad lane (r mod 16) / 4 by DPP (quad_perm [j,j,j,j]), so a
-// block takes 4 ds_read_b128 per lane instead of 16 (issue slots on the chain's wave) and 16
-// VGPRs instead of 64 (generated by the loop in this comment's commit: round r -> q{r/16}{r%4}).
-template <bool MIS>
-__device__ __forceinline__ void quad_block_regs(uint32_t (&x)[4], const uint4 (&K)[4], uint3 sh, uint32_t msk) {
-    uint32_t p0 = x[0], p1 = x[1], p2 = x[2], p3 = x[3], h, g, r_, f_, s_, t_;
-    (void)t_;
-    asm volatile(DM_QS_PROLOGUE_AT("q00", DM_QS_ALIGN_MIS, "[0,0,0,0]")
-                 DM_QS_GROUP0Q("q01", "[0,0,0,0]", "q02", "[0,0,0,0]", "q03", "[0,0,0,0]", "q00", "[1,1,1,1]")
-                 DM_QS_STEPS4Q("q01", "[1,1,1,1]", "q02", "[1,1,1,1]", "q03", "[1,1,1,1]", "q00", "[2,2,2,2]")
-                 DM_QS_STEPS4Q("q01", "[2,2,2,2]", "q02", "[2,2,2,2]", "q03", "[2,2,2,2]", "q00", "[3,3,3,3]")
-                 DM_QS_STEPS4Q("q01", "[3,3,3,3]", "q02", "[3,3,3,3]", "q03", "[3,3,3,3]", "q10", "[0,0,0,0]")
-                 DM_QS_STEPS4Q("q11", "[0,0,0,0]", "q12", "[0,0,0,0]", "q13", "[0,0,0,0]", "q10", "[1,1,1,1]")
-                 DM_QS_STEPS4Q("q11", "[1,1,1,1]", "q12", "[1,1,1,1]", "q13", "[1,1,1,1]", "q10", "[2,2,2,2]")
-                 DM_QS_STEPS4Q("q11", "[2,2,2,2]", "q12", "[2,2,2,2]", "q13", "[2,2,2,2]", "q10", "[3,3,3,3]")
-                 DM_QS_STEPS4Q("q11", "[3,3,3,3]", "q12", "[3,3,3,3]", "q13", "[3,3,3,3]", "q20", "[0,0,0,0]")
-                 DM_QS_STEPS4Q("q21", "[0,0,0,0]", "q22", "[0,0,0,0]", "q23", "[0,0,0,0]", "q20", "[1,1,1,1]")
-                 DM_QS_STEPS4Q("q21", "[1,1,1,1]", "q22", "[1,1,1,1]", "q23", "[1,1,1,1]", "q20", "[2,2,2,2]")
-                 DM_QS_STEPS4Q("q21", "[2,2,2,2]", "q22", "[2,2,2,2]", "q23", "[2,2,2,2]", "q20", "[3,3,3,3]")
-                 DM_QS_STEPS4Q("q21", "[3,3,3,3]", "q22", "[3,3,3,3]", "q23", "[3,3,3,3]", "q30", "[0,0,0,0]")
-                 DM_QS_STEPS4Q("q31", "[0,0,0,0]", "q32", "[0,0,0,0]", "q33", "[0,0,0,0]", "q30", "[1,1,1,1]")
-                 DM_QS_STEPS4Q("q31", "[1,1,1,1]", "q32", "[1,1,1,1]", "q33", "[1,1,1,1]", "q30", "[2,2,2,2]")
-                 DM_QS_STEPS4Q("q31", "[2,2,2,2]", "q32", "[2,2,2,2]", "q33", "[2,2,2,2]", "q30", "[3,3,3,3]")
-                 DM_QS_TAILQ("q31", "[3,3,3,3]", "q32", "[3,3,3,3]", "q33", "[3,3,3,3]")
-                 : [a] "+v"(p0), [b] "+v"(p1), [c] "+v"(p2), [d] "+v"(p3), [h] "=&v"(h), [g] "=&v"(g),
-                   [x0] "+v"(x[0]), [x1] "+v"(x[1]), [x2] "+v"(x[2]), [x3] "+v"(x[3]), [r] "=&v"(r_),
-                   [f] "=&v"(f_), [s] "=&v"(s_) DM_QS_XOUT
-                 : [mis] "i"(MIS ? 1 : 0), [sh] "v"(sh.x), [msk] "v"(msk),
-                   [q00] "v"(K[0].x), [q01] "v"(K[0].y), [q02] "v"(K[0].z), [q03] "v"(K[0].w),
-                   [q10] "v"(K[1].x), [q11] "v"(K[1].y), [q12] "v"(K[1].z), [q13] "v"(K[1].w),
-                   [q20] "v"(K[2].x), [q21] "v"(K[2].y), [q22] "v"(K[2].z), [q23] "v"(K[2].w),
-                   [q30] "v"(K[3].x), [q31] "v"(K[3].y), [q32] "v"(K[3].z), [q33] "v"(K[3].w) DM_QS_XIN);
+// The register path: quad_block_skewed with the block's 64 words of -(K+W) in registers and the
+// blocks of a ring stage run as ONE step stream.  The words are spread over the 4 lanes of a
+// quad: lane j's K[t] holds rounds 16t + 4j .. 16t + 4j + 3, and round r's step reads its word
+// from quad lane (r mod 16) / 4 by DPP (quad_perm [j,j,j,j]), so a block takes 4 ds_read_b128 per
+// lane instead of 16 (issue slots on the chain's wave) and 16 VGPRs instead of 64.
+//
+// 64 = 0 mod 4, so the role registers keep their names across a block boundary, and steps 64 and
+// 65 of block b (the a-triple's rounds 62, 63) ARE steps 0 and 1 of block b+1 (the e-triple's
+// rounds 0, 1): the stream fills once per stage (prologue, two stale a-steps and their repair)
+// and drains once (DM_QS_TAILQ); the 7 boundaries in between are DM_QS_LINKQ, 17 instructions
+// on top of the steps instead of 30.  At a link the two lane types feed forward at different
+// times, each with bank-masked VOP2-DPP ops only (0x3 = e-quads, 0xc = a-quads):
+//   e-quads: h += x3 before step 63, whose X6 update then gives -(h' + KW0) from x3 directly;
+//            e, f, g (P0..P2) += x between steps 63 and 64, then x = P (copies) before the
+//            steps that modify or overwrite each P.
+//   a-quads: x += P as soon as each word is final (d after step 62, c after 63, b after 64, a
+//            after 65) while P stays raw for rounds 62, 63; P0, P2, P3 = x after step 65 (P1 is
+//            the next write).
+//   The exchange (HN) of steps 63..65 is split by lane type, because what the other quad must
+//   hand over is not what it is still working on: the e-triple takes d' of its rounds 0..2 from
+//   the a-quad's x (x1, x0, x3: already fed forward) instead of its raw P; the a-triple takes
+//   T1(63) = e(64) - d(63) from the raw e(64) before the e-quad feeds P0 forward, and
+//   T1(0)  = e'(1) - d'(0) with d' from its own x1.
+// Every DPP source VGPR is still written at least two instructions earlier.  N0..N2 = the NEXT
+// block's rounds 0..2 (its K[0].x/y/z, quad lane 0).
+#define DM_QS_HNB(HN, A, B, BANKS) "v_sub_u32_dpp %[" HN "], %[" A "], %[" B "] row_ror:8 row_mask:0xf bank_mask:" BANKS "\n\t"
+#define DM_QS_ADDB(D, A, B, BANKS) "v_add_u32_dpp %[" D "], %[" A "], %[" B "] quad_perm:[0,1,2,3] row_mask:0xf bank_mask:" BANKS "\n\t"
+#define DM_QS_MOVB(D, S, BANKS) "v_mov_b32_dpp %[" D "], %[" S "] quad_perm:[0,1,2,3] row_mask:0xf bank_mask:" BANKS "\n\t"
+#define DM_QS_KWN(X6, S, N) "v_sub_u32_dpp %[" X6 "], %[" N "], %[" S "] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0x3\n\t"
+#define DM_QS_ADD3(X7, H) "v_add3_u32 %[" X7 "], %[s], %[f], %[" H "]\n\t"
+#define DM_QS_LINKQ(V0, Q0, V1, Q1, V2, Q2, N0, N1, N2)                                          \
+    DM_QS_STEP_Q("a", "b", "c", "d", "h", "g", V0, Q0) DM_QS_STEP_Q("d", "a", "b", "c", "g", "h", V1, Q1) \
+    DM_QS_STEP_Q("c", "d", "a", "b", "h", "g", V2, Q2)                                           \
+    DM_QS_ADDB("x1", "x1", "b", "0xc") DM_QS_ADDB("x3", "x3", "d", "0x3")                        \
+    /* step 63: e round 63 + H of round 0'; a round 61 */                                        \
+    DM_QS_HEAD("b", "c", "d") DM_QS_KWN("d", "x3", N0) DM_QS_SIGMA                               \
+    DM_QS_HNB("h", "x1", "d", "0x3") DM_QS_HNB("h", "b", "d", "0xc") DM_QS_ADD3("a", "g")        \
+    DM_QS_ADDB("b", "x1", "b", "0x3") DM_QS_ADDB("c", "x2", "c", "0x3")                          \
+    DM_QS_HNB("g", "a", "c", "0xc") DM_QS_ADDB("x0", "x0", "a", "0xc")                           \
+    DM_QS_ADDB("a", "a", "x0", "0x3") DM_QS_MOVB("x2", "c", "0x3")                               \
+    /* step 64: e round 0'; a round 62 */                                                        \
+    DM_QS_HEAD("a", "b", "c") DM_QS_KWN("c", "c", N1) DM_QS_SIGMA                                \
+    DM_QS_HNB("g", "x0", "c", "0x3") DM_QS_ADD3("d", "h")                                        \
+    DM_QS_ADDB("x3", "x3", "d", "0xc") DM_QS_MOVB("x1", "b", "0x3") DM_QS_MOVB("x0", "a", "0x3") \
+    /* step 65: e round 1'; a round 63 + T1 of round 0' */                                       \
+    DM_QS_HEAD("d", "a", "b") DM_QS_KWN("b", "b", N2) DM_QS_SIGMA                                \
+    DM_QS_HNB("h", "x3", "b", "0x3") DM_QS_HNB("h", "d", "x1", "0xc") DM_QS_ADD3("c", "g")       \
+    DM_QS_ADDB("x2", "x2", "c", "0xc") DM_QS_MOVB("a", "x0", "0xc") DM_QS_MOVB("d", "x3", "0xc") \
+    DM_QS_MOVB("c", "x2", "0xc")
+// steps 4..59 of a block from its registers
+#define DM_QS_BODYQ                                                                              \
+    DM_QS_STEPS4Q("q01", "[1,1,1,1]", "q02", "[1,1,1,1]", "q03", "[1,1,1,1]", "q00", "[2,2,2,2]") \
+    DM_QS_STEPS4Q("q01", "[2,2,2,2]", "q02", "[2,2,2,2]", "q03", "[2,2,2,2]", "q00", "[3,3,3,3]") \
+    DM_QS_STEPS4Q("q01", "[3,3,3,3]", "q02", "[3,3,3,3]", "q03", "[3,3,3,3]", "q10", "[0,0,0,0]") \
+    DM_QS_STEPS4Q("q11", "[0,0,0,0]", "q12", "[0,0,0,0]", "q13", "[0,0,0,0]", "q10", "[1,1,1,1]") \
+    DM_QS_STEPS4Q("q11", "[1,1,1,1]", "q12", "[1,1,1,1]", "q13", "[1,1,1,1]", "q10", "[2,2,2,2]") \
+    DM_QS_STEPS4Q("q11", "[2,2,2,2]", "q12", "[2,2,2,2]", "q13", "[2,2,2,2]", "q10", "[3,3,3,3]") \
+    DM_QS_STEPS4Q("q11", "[3,3,3,3]", "q12", "[3,3,3,3]", "q13", "[3,3,3,3]", "q20", "[0,0,0,0]") \
+    DM_QS_STEPS4Q("q21", "[0,0,0,0]", "q22", "[0,0,0,0]", "q23", "[0,0,0,0]", "q20", "[1,1,1,1]") \
+    DM_QS_STEPS4Q("q21", "[1,1,1,1]", "q22", "[1,1,1,1]", "q23", "[1,1,1,1]", "q20", "[2,2,2,2]") \
+    DM_QS_STEPS4Q("q21", "[2,2,2,2]", "q22", "[2,2,2,2]", "q23", "[2,2,2,2]", "q20", "[3,3,3,3]") \
+    DM_QS_STEPS4Q("q21", "[3,3,3,3]", "q22", "[3,3,3,3]", "q23", "[3,3,3,3]", "q30", "[0,0,0,0]") \
+    DM_QS_STEPS4Q("q31", "[0,0,0,0]", "q32", "[0,0,0,0]", "q33", "[0,0,0,0]", "q30", "[1,1,1,1]") \
+    DM_QS_STEPS4Q("q31", "[1,1,1,1]", "q32", "[1,1,1,1]", "q33", "[1,1,1,1]", "q30", "[2,2,2,2]") \
+    DM_QS_STEPS4Q("q31", "[2,2,2,2]", "q32", "[2,2,2,2]", "q33", "[2,2,2,2]", "q30", "[3,3,3,3]")
+// a block's first four steps: filling the stream (first block of a stage) / already running
+#define DM_QS_FILLQ                                                                              \
+    DM_QS_PROLOGUE_AT("q00", DM_QS_ALIGN_MIS, "[0,0,0,0]")                                       \
+    DM_QS_GROUP0Q("q01", "[0,0,0,0]", "q02", "[0,0,0,0]", "q03", "[0,0,0,0]", "q00", "[1,1,1,1]")
+#define DM_QS_CONTQ                                                                              \
+    DM_QS_ALIGN_MIS                                                                              \
+    DM_QS_STEP_Q("c", "d", "a", "b", "h", "g", "q03", "[0,0,0,0]") DM_QS_STEP_Q("b", "c", "d", "a", "g", "h", "q00", "[1,1,1,1]")
+#define DM_QS_ENDLINKQ DM_QS_LINKQ("q31", "[3,3,3,3]", "q32", "[3,3,3,3]", "q33", "[3,3,3,3]", "n0", "n1", "n2")
+#define DM_QS_ENDTAILQ DM_QS_TAILQ("q31", "[3,3,3,3]", "q32", "[3,3,3,3]", "q33", "[3,3,3,3]")
+#define DM_QS_STATE [a] "+v"(P[0]), [b] "+v"(P[1]), [c] "+v"(P[2]), [d] "+v"(P[3]),              \
+                    [x0] "+v"(x[0]), [x1] "+v"(x[1]), [x2] "+v"(x[2]), [x3] "+v"(x[3]),           \
+                    [r] "=&v"(r_), [f] "=&v"(f_), [s] "=&v"(s_)
+#define DM_QS_KIN [mis] "i"(MIS ? 1 : 0), [sh] "v"(sh.x), [msk] "v"(msk),                        \
+                  [q00] "v"(K[0].x), [q01] "v"(K[0].y), [q02] "v"(K[0].z), [q03] "v"(K[0].w),     \
+                  [q10] "v"(K[1].x), [q11] "v"(K[1].y), [q12] "v"(K[1].z), [q13] "v"(K[1].w),     \
+                  [q20] "v"(K[2].x), [q21] "v"(K[2].y), [q22] "v"(K[2].z), [q23] "v"(K[2].w),     \
+                  [q30] "v"(K[3].x), [q31] "v"(K[3].y), [q32] "v"(K[3].z), [q33] "v"(K[3].w)
+
+// Block k of a ring stage on the register path; each block is one asm statement (hipcc puts an
+// s_nop between asm statements that share registers, and the K+W loads between them).  P, h, g:
+// the stream's state, carried from block to block.  N = K[0] of block k + 1.
+template <bool MIS, int K8>
+__device__ __forceinline__ void quad_block_regs(uint32_t (&x)[4], uint32_t (&P)[4], uint32_t& h, uint32_t& g,
+                                                const uint4 (&K)[4], const uint4& N, uint3 sh, uint32_t msk) {
+    uint32_t r_, f_, s_;
+    if constexpr (K8 == 0) {
+        asm volatile(DM_QS_FILLQ DM_QS_BODYQ DM_QS_ENDLINKQ
+                     : DM_QS_STATE, [h] "=&v"(h), [g] "=&v"(g)
+                     : DM_QS_KIN, [n0] "v"(N.x), [n1] "v"(N.y), [n2] "v"(N.z));
+    } else if constexpr (K8 < kQuadBlocks - 1) {
+        asm volatile(DM_QS_CONTQ DM_QS_BODYQ DM_QS_ENDLINKQ
+                     : DM_QS_STATE, [h] "+v"(h), [g] "+v"(g)
+                     : DM_QS_KIN, [n0] "v"(N.x), [n1] "v"(N.y), [n2] "v"(N.z));
+    } else {
+        asm volatile(DM_QS_CONTQ DM_QS_BODYQ DM_QS_ENDTAILQ
+                     : DM_QS_STATE, [h] "+v"(h), [g] "+v"(g)
+                     : DM_QS_KIN);
+    }
 }
 
 // One ring stage (8 blocks) when every leaf of the wave has all 8: each block's 64 K+W words go
-// to registers in one burst while the previous block runs (one s_waitcnt per block instead of
-// one per 4 rounds), and no per-block branch.  kw: this lane's column (quad lane p's groups
-// 4t + p, see quad_block_regs).
+// to registers in one burst two blocks ahead (one s_waitcnt per block instead of one per 4
+// rounds; three register sets, because a block's last three steps already read the next block's
+// first words), and no per-block branch.  kw: this lane's column (quad lane p's groups 4t + p,
+// see quad_block_regs).
+template <int G, int ROW, bool MIS, int K8 = 0>
+__device__ __forceinline__ void quad_stage_blocks(uint32_t (&x)[4], uint32_t (&P)[4], uint32_t& h, uint32_t& g,
+                                                  uint4 (&S)[3][4], const uint4* kw, uint3 sh, uint32_t msk) {
+    __builtin_amdgcn_s_waitcnt(kLgkmWait0);
+    if constexpr (K8 + 2 < kQuadBlocks) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) S[(K8 + 2) % 3][t] = kw[(K8 + 2) * ROW + 4 * t * G];
+    }
+    quad_block_regs<MIS, K8>(x, P, h, g, S[K8 % 3], S[(K8 + 1) % 3][0], sh, msk);
+    if constexpr (K8 + 1 < kQuadBlocks) quad_stage_blocks<G, ROW, MIS, K8 + 1>(x, P, h, g, S, kw, sh, msk);
+}
 template <int G, int ROW, bool MIS>
 __device__ __forceinline__ void quad_stage_regs(uint32_t (&x)[4], const uint4* kw, uint3 sh, uint32_t msk) {
-    uint4 A[4], B[4];
+    uint4 S[3][4];
+    uint32_t P[4] = {x[0], x[1], x[2], x[3]}, h, g;
 #pragma unroll
-    for (int t = 0; t < 4; t++) A[t] = kw[4 * t * G];
+    for (int k = 0; k < 2; k++) {
 #pragma unroll
-    for (int k = 0; k < kQuadBlocks; k += 2) {
-        __builtin_amdgcn_s_waitcnt(kLgkmWait0);
-#pragma unroll
-        for (int t = 0; t < 4; t++) B[t] = kw[(k + 1) * ROW + 4 * t * G];
-        quad_block_regs<MIS>(x, A, sh, msk);
-        __builtin_amdgcn_s_waitcnt(kLgkmWait0);
-        if (k + 2 < kQuadBlocks) {
-#pragma unroll
-            for (int t = 0; t < 4; t++) A[t] = kw[(k + 2) * ROW + 4 * t * G];
-        }
-        quad_block_regs<MIS>(x, B, sh, msk);
+        for (int t = 0; t < 4; t++) S[k][t] = kw[k * ROW + 4 * t * G];
     }
+    quad_stage_blocks<G, ROW, MIS>(x, P, h, g, S, kw, sh, msk);
 }
 
 template <bool TABLE, bool ALIGNED, bool COMPACT>
@@ -873,11 +947,7 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
         const uint32_t p = lane & 3;
         const uint64_t iq = first + cq;
         const LeafView vq = leaf_view<TABLE>(a, iq);
-#if DM_QS_DEEP3
-        const uint3 sh = role_a ? make_uint3(2, 13, 22) : make_uint3(6, 11, 25);
-#else
         const uint3 sh = make_uint3(role_a ? (p == 0 ? 2 : p == 1 ? 13 : 22) : (p == 0 ? 6 : p == 1 ? 11 : 25), 0, 0);
-#endif
         const uint32_t msk = role_a ? 0u : ~0u;
         uint32_t st0[8];
         if (vq.active) load_or_init_state(a, iq, st0);
@@ -897,29 +967,33 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
         uint32_t xf[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) xf[k] = x[k];
-        // a leaf of the wave ends strictly inside stage it
-        auto partial = [&](uint64_t it) {
-            const uint64_t b0 = it * kQuadBlocks;
-            return __any(vq.active && vq.nb > b0 && vq.nb < b0 + kQuadBlocks);
-        };
-        for (uint64_t it = 0; it < NI;) {
-            // runs of whole stages: their own loop, so the register path compiles (and is counted
-            // by deoss_amd/isa.py) without the per-block path inside it
-            for (; it < NI && !partial(it); it++) {
+        const uint64_t NS = uniform_u64(NI);
+        for (uint64_t it = 0; it < NS;) {
+            // A run of whole stages, its own loop, so the register path compiles (and is counted by
+            // deoss_amd/isa.py) without the per-block path inside it.  Its length is known before it
+            // starts: it ends where the first of the leaves still running ends, be that at a stage
+            // boundary or inside stage nb / 8.  So every leaf still running runs all of the run and
+            // xf is set once at its end: a scalar trip count, no vote and no copies per stage on the
+            // chain's wave.  A wave of mixed lengths takes one run per distinct leaf end.
+            const bool running = vq.active && vq.nb > it * kQuadBlocks;
+            const uint64_t end = uniform_u64(wave_min_u64(running ? vq.nb / kQuadBlocks : NS));
+            for (; it < end; it++) {
                 quad_stage_regs<G, ROW, COMPACT>(x, col + (it % kLatRing) * 16 * G + p * G, sh, msk);
-                if (vq.nb > it * kQuadBlocks) {   // this stage advanced the leaf
-#pragma unroll
-                    for (int k = 0; k < 4; k++) xf[k] = x[k];
-                }
                 __syncthreads();
             }
-            if (it == NI) break;
+            if (running) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) xf[k] = x[k];
+            }
+            if (it == NS) break;
+            // a leaf of the wave ends strictly inside stage it: the per-block path; else the next run
+            if (!__any(vq.active && vq.nb > it * kQuadBlocks && vq.nb < (it + 1) * kQuadBlocks)) continue;
             const uint4* kw = col + (it % kLatRing) * 16 * G;
             const uint64_t b0 = it * kQuadBlocks;
             for (uint32_t k = 0; k < kQuadBlocks; k++) {
                 const uint4* kb = kw + k * ROW;
                 if (b0 + k < vq.nb)
-                    quad_block_skewed(x, [kb](int g) { return kb[g * G]; }, sh, msk);
+                    quad_block_skewed<COMPACT>(x, [kb](int g) { return kb[g * G]; }, sh, msk);
             }
             if (vq.nb > b0) {
 #pragma unroll

@@ -123,11 +123,11 @@ def analyse(asm: str, sym: str = K1_SYMBOL) -> dict:
 
 def analyse_split(asm: str, sym: str) -> dict:
     loops = list(_loops(_function_body(asm, sym)))
-    # K1Q runs whole ring stages (8 blocks from registers: 8 x 66 steps, each ending in one
-    # v_add3_u32; 4 ds_read_b128 per block since the words are spread over a quad's lanes) when
-    # every leaf of the wave has them: that loop is the bench path; otherwise the per-block loop
-    # (16 reads)
-    stage = _smallest(loops, lambda l: sum(x.startswith("v_add3_u32") for x in l) >= 8 * 66
+    # K1Q runs whole ring stages (8 blocks from registers as one step stream: 8 x 64 steps plus
+    # the two that drain it, each ending in one v_add3_u32; 4 ds_read_b128 per block since the
+    # words are spread over a quad's lanes) when no leaf of the wave ends inside them: that loop
+    # is the bench path; otherwise the per-block loop (16 reads)
+    stage = _smallest(loops, lambda l: sum(x.startswith("v_add3_u32") for x in l) >= 8 * 64 + 2
                       and sum(x.startswith("ds_read_b128") for x in l) >= 32)
     if stage is not None:
         prod = _smallest(loops, lambda l: sum(x.startswith("ds_write_b128") for x in l) >= 16)
