@@ -19,13 +19,6 @@
 
 namespace {
 
-// Go's error text for an errno: strerror with a lower-case first letter ("no such file or directory").
-std::string go_errno(int e) {
-    std::string m = std::strerror(e);
-    if (!m.empty()) m[0] = (char)std::tolower((unsigned char)m[0]);
-    return m;
-}
-
 struct FileSet {
     std::vector<std::string> path;
     std::vector<uint64_t> size;
@@ -38,7 +31,7 @@ struct FileSet {
 };
 
 // types.go:24-33: files are opened and read in order and the first failure is returned, with Go's
-// messages: "open <path>: <errno text>", "read <path>: is a directory".
+// messages: "open <path>: <errno text>" (go_errno, fp_files.hpp), "read <path>: is a directory".
 int open_files(dm_ctx* c, const char* const* paths, uint64_t n, FileSet& fs) {
     // Keep every file open when the descriptor limit allows (Go raises the soft limit to the hard
     // one at start-up; Python keeps 1,024): striped reads touch every file once per step, and

@@ -37,8 +37,9 @@ int dm_fragment_lookup(dm_rs* r, const char* path, uint64_t segment, const uint8
     const uint64_t size = fs.size[0];
     if (size == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
     RC_TRY(process_check(r, size, segment));
-    const int k = r->k, m = r->m, total = k + m;
-    const uint64_t frag = segment / (uint64_t)k, pbytes = (uint64_t)m * frag;
+    const FpLayout lay(r->k, r->m, segment);
+    const int total = lay.total;
+    const uint64_t frag = lay.frag, pbytes = lay.pbytes;
     if (out && out_cap < frag)
         return fail(c, DM_ERR_INVALID, "dm_fragment_lookup: out holds %llu bytes, a fragment is %llu",
                     (unsigned long long)out_cap, (unsigned long long)frag);
@@ -49,7 +50,7 @@ int dm_fragment_lookup(dm_rs* r, const char* path, uint64_t segment, const uint8
                                   ? env_bytes("DEOSS_FL_WINDOW_BYTES", kFlWindowBytes)
                                   : std::min(kFlWindowMaxBytes, std::max(kFlWindowBytes, size / 4));
     const uint64_t win = std::min(nseg, std::max<uint64_t>(1, want_win / segment));
-    const uint64_t spd = std::min(win, std::max<uint64_t>(1, env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes) / segment));
+    const uint64_t spd = std::min(win, fp_slots(lay, env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes)).spd);
     const uint64_t nwin = ceil_div(nseg, win), per = win * (uint64_t)total;   // fragments per full window
     Dev& d = c->devs[g];
     RsLane& L = rs_ln(r, d);
@@ -86,17 +87,13 @@ int dm_fragment_lookup(dm_rs* r, const char* path, uint64_t segment, const uint8
     uint8_t* data[2] = {d.data.u8(), d.data.u8() + win * segment};
     uint8_t* par[2] = {L.work.u8(), L.work.u8() + win * pbytes};
     uint8_t* hdig = L.fp_slot[kFlSlots].u8();
-    // one leaf table for both halves: fragment j of segment t of half b (data fragments are
-    // segment slices, parity fragments live in the parity half)
-    std::vector<uint64_t> addr(2 * per), lens(2 * per, frag);
-    for (int b = 0; b < 2; b++)
-        for (uint64_t t = 0; t < win; t++)
-            for (int j = 0; j < total; j++)
-                addr[b * per + t * total + j] = reinterpret_cast<uint64_t>(
-                    j < k ? data[b] + t * segment + (uint64_t)j * frag : par[b] + t * pbytes + (uint64_t)(j - k) * frag);
-    RC_TRY(tables_begin(c, d, 2 * per * 16 + 1024));
-    RC_TRY(upload(c, d, s, d.tab_addr, addr.data(), addr.size() * 8));
-    RC_TRY(upload(c, d, s, d.tab_len, lens.data(), lens.size() * 8));
+    // one leaf table for both halves, fragments only: fragment j of segment t of half b at
+    // b * per + t * total + j
+    std::vector<uint64_t> addr(2 * per), lens(2 * per);
+    const FpPiece halves[2] = {{data[0], par[0], win}, {data[1], par[1], win}};
+    leaf_table(lay, halves, 2, false, addr.data(), lens.data());
+    dm::LeafArgs both;
+    RC_TRY(table_args(c, d, s, addr.data(), lens.data(), 2 * per, 1024, &both));
     const int readers = (int)std::min<uint64_t>(64, env_bytes("DEOSS_FP_READERS", kFpReaders));
     // window w's names (in segment, fragment order) against `want`: 1 found (its bytes copied to
     // out), 0 not in this window, -1 the copy failed.  Window w's half is neither re-filled nor its
@@ -111,8 +108,7 @@ int dm_fragment_lookup(dm_rs* r, const char* path, uint64_t segment, const uint8
             *found = 1;
             if (seg_idx) *seg_idx = w * win + t;
             if (frag_idx) *frag_idx = j;
-            const uint8_t* src = j < k ? data[w % 2] + t * segment + (uint64_t)j * frag
-                                       : par[w % 2] + t * pbytes + (uint64_t)(j - k) * frag;
+            const uint8_t* src = lay.frag_ptr(data[w % 2], par[w % 2], t, j);
             if (!out) return 1;
             // on the copy stream: the compute stream may already hold the next window's chains
             const bool ok = hipMemcpyAsync(out, src, frag, hipMemcpyDeviceToHost, cp) == hipSuccess &&
@@ -168,23 +164,12 @@ int dm_fragment_lookup(dm_rs* r, const char* path, uint64_t segment, const uint8
         // waiting for another window's chains (a window's chain, ~0.13 s, is about its read time)
         if ((hit = scan_upto(w, true)) != 0) break;
         HIP_TRY(hipStreamWaitEvent(s, ev.copied[b], 0));
-        dm::RsArgs a{};
-        for (int j = 0; j < k; j++) a.in[j] = data[b] + (uint64_t)j * frag;
-        for (int i = 0; i < m; i++) a.out[i] = par[b] + (uint64_t)i * frag;
-        a.in_seg_stride = segment;
-        a.out_seg_stride = pbytes;
-        a.units_per_seg = frag / 16;
-        a.nseg = ns;
-        a.table = static_cast<const uint2*>(r->enc_tab.p);
-        a.nout = (uint32_t)m;
-        launch_rs(d, s, k, a);
-        HIP_TRY(hipGetLastError());
-        dm::LeafArgs la{};
-        la.addrs = static_cast<const uint64_t*>(d.tab_addr.p) + b * per;
-        la.lens = static_cast<const uint64_t*>(d.tab_len.p) + b * per;
+        HIP_TRY(launch_rs(d, s, lay.k, rs_encode_args(r, data[b], segment, par[b], pbytes, frag, ns)));
+        dm::LeafArgs la = both;   // this half's rows of the table, its part of the digests
+        la.addrs += b * per;
+        la.lens += b * per;
         la.nleaves = ns * (uint64_t)total;
-        la.byte_end = ~0ull;
-        la.digests = d.leaves.u8() + b * per * 32;
+        la.digests += b * per * 32;
         RC_TRY(launch_leaves(c, d, s, la, true, true, pick_leaf_kernel(c, d, la.nleaves)));
         HIP_TRY(hipMemcpyAsync(hdig + b * per * 32, la.digests, la.nleaves * 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipEventRecord(ev.hashed[b], s));

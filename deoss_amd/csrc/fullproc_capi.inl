@@ -22,20 +22,11 @@ namespace {
 
 constexpr uint64_t kFpSlotBytes = 64ull << 20;         // pinned slot (whole segments / parity sets)
 constexpr int kFpSlots = 4;                             // = dm_rs::fp_slot
-constexpr int kFpWritersPerSlot = 4;                    // background write jobs per parity slot
 constexpr size_t kFpDataWriters = 8;                    // jobs copying data fragments / segments from the file
 constexpr int kFpReaders = 8;                           // pread threads per slot (phase A gates the leaf pass)
 
-struct FdGuard {
-    int fd = -1;
-    ~FdGuard() {
-        if (fd >= 0) ::close(fd);
-    }
-};
 constexpr uint64_t kFpWindowBytes = 32ull << 30;        // file bytes per GPU pass (+ 2x parity in HBM)
 constexpr uint64_t kFpStripeMinSegs = 4;                // windows of at least this many segments read in stripes
-
-std::atomic<uint64_t> g_fp_seq{0};
 
 // DEOSS_FP_TRACE=1: phase times of each dm_full_processing window on stderr (diagnostics)
 struct FpTrace {
@@ -46,141 +37,6 @@ struct FpTrace {
             std::fprintf(stderr, "[fp] %-28s %8.1f ms\n", what,
                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
-};
-
-uint64_t env_bytes(const char* name, uint64_t dflt) {
-    const char* v = std::getenv(name);
-    const unsigned long long x = v ? std::strtoull(v, nullptr, 10) : 0;
-    return x ? (uint64_t)x : dflt;
-}
-
-std::string hex32(const uint8_t* d) {
-    static const char* x = "0123456789abcdef";
-    std::string s(64, '0');
-    for (int i = 0; i < 32; i++) {
-        s[2 * i] = x[d[i] >> 4];
-        s[2 * i + 1] = x[d[i] & 15];
-    }
-    return s;
-}
-
-// os.WriteFile(path, data, os.ModePerm), as the Go shim writes fragments; "" on success.
-std::string write_whole(const std::string& path, const uint8_t* p, uint64_t len) {
-    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0777);
-    if (fd < 0) return "open " + path + ": " + go_errno(errno);
-    uint64_t done = 0;
-    while (done < len) {
-        const ssize_t w = ::write(fd, p + done, len - done);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) {
-            const int e = w < 0 ? errno : EIO;
-            ::close(fd);
-            return "write " + path + ": " + go_errno(e);
-        }
-        done += (uint64_t)w;
-    }
-    if (::close(fd) != 0) return "close " + path + ": " + go_errno(errno);
-    return "";
-}
-
-// os.MkdirAll(dir, 0755)
-std::string mkdir_all(const std::string& dir) {
-    for (size_t i = 1; i <= dir.size(); i++) {
-        if (i < dir.size() && dir[i] != '/') continue;
-        const std::string p = dir.substr(0, i);
-        struct stat st {};
-        if (::stat(p.c_str(), &st) == 0) {
-            if (!S_ISDIR(st.st_mode)) return "mkdir " + p + ": not a directory";
-            continue;
-        }
-        if (::mkdir(p.c_str(), 0755) != 0 && errno != EEXIST) return "mkdir " + p + ": " + go_errno(errno);
-    }
-    return "";
-}
-
-struct FpFile {          // one file to write: its bytes (memory, or a range of an open file) and temporary name
-    const uint8_t* src;
-    uint64_t len;
-    std::string tmp;
-    int in_fd = -1;         // >= 0: the bytes are [in_off, in_off + len) of this file (copied in the kernel)
-    uint64_t in_off = 0;
-};
-
-// A file range into a new file: copy_file_range (page cache to page cache in the kernel, no user
-// copy), or pread / write through a bounce buffer where the kernel cannot.
-std::string copy_whole(const std::string& path, int in_fd, uint64_t off, uint64_t len) {
-    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0777);
-    if (fd < 0) return "open " + path + ": " + go_errno(errno);
-    uint64_t done = 0;
-    bool kernel = true;
-    std::vector<uint8_t> bounce;
-    while (done < len) {
-        if (kernel) {
-            loff_t io = (loff_t)(off + done);
-            const ssize_t w = ::copy_file_range(in_fd, &io, fd, nullptr, len - done, 0);
-            if (w > 0) {
-                done += (uint64_t)w;
-                continue;
-            }
-            if (w < 0 && errno == EINTR) continue;
-            if (w < 0 && errno != EXDEV && errno != ENOSYS && errno != EINVAL && errno != EOPNOTSUPP) {
-                const int e = errno;
-                ::close(fd);
-                return "write " + path + ": " + go_errno(e);
-            }
-            kernel = false;   // 0 (short source) or unsupported: finish through user space
-            bounce.resize(8ull << 20);
-        }
-        const uint64_t n = std::min<uint64_t>(bounce.size(), len - done);
-        const ssize_t r = ::pread(in_fd, bounce.data(), n, (off_t)(off + done));
-        if (r <= 0) {
-            ::close(fd);
-            return "read: " + (r < 0 ? go_errno(errno) : std::string("unexpected EOF"));
-        }
-        for (ssize_t put = 0; put < r;) {
-            const ssize_t w = ::write(fd, bounce.data() + put, (size_t)(r - put));
-            if (w < 0 && errno == EINTR) continue;
-            if (w <= 0) {
-                const int e = w < 0 ? errno : EIO;
-                ::close(fd);
-                return "write " + path + ": " + go_errno(e);
-            }
-            put += w;
-        }
-        done += (uint64_t)r;
-    }
-    if (::close(fd) != 0) return "close " + path + ": " + go_errno(errno);
-    return "";
-}
-
-// Background writes out of one pinned slot; wait() joins them before the slot is refilled.
-struct SlotWrites {
-    std::vector<std::future<std::string>> jobs;
-    void start(std::vector<FpFile> files, size_t jobs_max = kFpWritersPerSlot) {
-        const size_t J = std::min<size_t>(jobs_max, files.size());
-        for (size_t j = 0; j < J; j++) {
-            std::vector<FpFile> mine;
-            for (size_t i = j; i < files.size(); i += J) mine.push_back(files[i]);
-            jobs.push_back(std::async(std::launch::async, [mine]() {
-                for (const auto& f : mine) {
-                    std::string e = f.in_fd >= 0 ? copy_whole(f.tmp, f.in_fd, f.in_off, f.len)
-                                                 : write_whole(f.tmp, f.src, f.len);
-                    if (!e.empty()) return e;
-                }
-                return std::string();
-            }));
-        }
-    }
-    std::string wait() {   // first error, once every job has finished
-        std::string err;
-        for (auto& j : jobs) {
-            std::string e = j.get();
-            if (err.empty()) err = e;
-        }
-        jobs.clear();
-        return err;
-    }
-    ~SlotWrites() { (void)wait(); }
 };
 
 constexpr uint64_t kFpKeepBytes = 4ull << 30;   // window scratch kept between dm_full_processing calls
@@ -200,15 +56,15 @@ struct FpEvents {
 // into one pinned slot, copied to HBM with one 2D copy (segment pitch), and two resumable leaf
 // launches absorb them: the ns segment chains (kit->comp[0]) and the ns chains of the data fragment
 // the stripe lies in (kit->comp[1]).  After the last stripe: RS over the window and one leaf launch
-// over the parity fragments (on s), then the fid over the segment digests.  d.leaves: segment t at
-// t, data fragment (t, q) at ns * (1 + q) + t, parity fragment (t, i) at ns * (1 + k) + t * m + i.
+// over the parity fragments (on s), then the fid over the segment digests.  d.leaves: the striped
+// order (FpLayout::striped_frag_slot).
 template <class TakeSlot>
 int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileSet& fs, uint64_t fbeg, uint64_t fend,
-                    uint64_t ns, uint64_t seg, uint64_t slot_cap, int readers, TakeSlot& take_slot,
+                    uint64_t ns, const FpLayout& L, uint64_t slot_cap, int readers, TakeSlot& take_slot,
                     bool (&busy)[kFpSlots], FpEvents& ev, uint8_t* parity, uint8_t* dfid, FpTrace& tr) {
     dm_ctx* c = r->c;
-    const int k = r->k, m = r->m;
-    const uint64_t frag = seg / (uint64_t)k;
+    const int k = L.k, m = L.m;
+    const uint64_t seg = L.seg, frag = L.frag;
     const uint64_t W = std::max<uint64_t>(64, (slot_cap / ns) / 64 * 64);   // slot row pitch
     std::vector<uint64_t> so0, sw0, so, sw;
     stripe_schedule(W, seg, so0, sw0);
@@ -230,7 +86,7 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
         for (uint64_t t = 0; t < ns; t++) addr[j * ns + t] = reinterpret_cast<uint64_t>(d.data.u8() + t * seg + so[j]);
     for (uint64_t i = 0; i < ns * m; i++) paddr[i] = reinterpret_cast<uint64_t>(parity + i * frag);
     RC_TRY(tables_begin(c, d, (addr.size() + lens.size() + 2 * ns * m) * 8 + 4096));
-    HIP_TRY(d.leaves.ensure(32 * ns * (1 + (uint64_t)(k + m))));
+    HIP_TRY(d.leaves.ensure(32 * L.leaves(ns)));
     RC_TRY(upload(c, d, s, d.tab_addr, addr.data(), addr.size() * 8));
     RC_TRY(upload(c, d, s, d.tab_len, lens.data(), lens.size() * 8));
     RC_TRY(upload(c, d, s, d.tab_first, paddr.data(), paddr.size() * 8));
@@ -268,7 +124,7 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
         la.byte_end = la.byte_off + w;
         la.state = frag_state;   // re-initialised where each fragment starts (byte_off 0)
         la.lens = static_cast<const uint64_t*>(d.tab_len.p) + ns;
-        la.digests = d.leaves.u8() + 32 * ns * (1 + q);
+        la.digests = d.leaves.u8() + 32 * L.striped_frag_slot(ns, 0, (int)q);
         HIP_TRY(hipStreamWaitEvent(kit->comp[1], ev.slot[sl], 0));
         RC_TRY(launch_leaves(c, d, kit->comp[1], la, true, true, kind));
     }
@@ -276,24 +132,10 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
     // RS after the last copy, then the parity fragments' chains (8 MiB: shorter than the segments')
     HIP_TRY(hipEventRecord(ev.copied, d.copy));
     HIP_TRY(hipStreamWaitEvent(s, ev.copied, 0));
-    dm::RsArgs a{};
-    for (int j = 0; j < k; j++) a.in[j] = d.data.u8() + (uint64_t)j * frag;
-    for (int i = 0; i < m; i++) a.out[i] = parity + (uint64_t)i * frag;
-    a.in_seg_stride = seg;
-    a.out_seg_stride = (uint64_t)m * frag;
-    a.units_per_seg = frag / 16;
-    a.nseg = ns;
-    a.table = static_cast<const uint2*>(r->enc_tab.p);
-    a.nout = (uint32_t)m;
-    launch_rs(d, s, k, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_rs(d, s, k, rs_encode_args(r, d.data.u8(), seg, parity, L.pbytes, frag, ns)));
     HIP_TRY(hipEventRecord(ev.rs, s));
-    dm::LeafArgs pa{};
-    pa.addrs = static_cast<const uint64_t*>(d.tab_first.p);
-    pa.lens = static_cast<const uint64_t*>(d.tab_ids.p);
-    pa.nleaves = ns * m;
-    pa.byte_end = ~0ull;
-    pa.digests = d.leaves.u8() + 32 * ns * (1 + (uint64_t)k);
+    const dm::LeafArgs pa =
+        table_args(d.tab_first.p, d.tab_ids.p, ns * m, d.leaves.u8() + 32 * L.striped_frag_slot(ns, 0, k));
     RC_TRY(launch_leaves(c, d, s, pa, true, true, pick_leaf_kernel(c, d, ns * m)));
     // the fid once the segment chains are done
     HIP_TRY(hipEventRecord(kit->ev[0], kit->comp[0]));
@@ -304,23 +146,21 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
     return DM_OK;
 }
 
-// Everything but the renames; `pend` collects (temporary name, digest slot) of every file written.
-int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::string& dir, uint64_t seg, int flags,
-                            std::vector<uint8_t>& segd, std::vector<uint8_t>& fragd,
-                            std::vector<std::pair<std::string, uint64_t>>& pend, uint8_t fid[32]) {
+// Everything but the renames; `out` collects every file written under its temporary name.
+int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out, uint64_t seg, int flags,
+                            std::vector<uint8_t>& segd, std::vector<uint8_t>& fragd, uint8_t fid[32]) {
     dm_ctx* c = r->c;
     const int g = (int)(&d - c->devs.data());   // the call's lane
     RsLane& L = rs_ln(r, d);
     hipStream_t s = d.stream;
-    const int k = r->k, m = r->m, total = k + m;
-    const uint64_t frag = seg / (uint64_t)k, pbytes = (uint64_t)m * frag;   // parity bytes per segment
+    const FpLayout lay(r->k, r->m, seg);
+    const int total = lay.total;
+    const uint64_t frag = lay.frag, pbytes = lay.pbytes;   // parity bytes per segment
     const uint64_t size = fs.size[0], nseg = ceil_div(size, seg);
     // test hooks (env, read per call): smaller slots / windows exercise slot reuse and multi-window fids
-    const uint64_t slot_bytes = env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes);
     const uint64_t window_bytes = env_bytes("DEOSS_FP_WINDOW_BYTES", kFpWindowBytes);
-    const uint64_t spd = std::max<uint64_t>(1, slot_bytes / seg);            // segments per data slot
-    const uint64_t spp = std::max<uint64_t>(1, slot_bytes / pbytes);         // segments per parity slot
-    const uint64_t slot_cap = std::max(spd * seg, spp * pbytes);
+    const FpSlots slots = fp_slots(lay, env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes));
+    const uint64_t spd = slots.spd, spp = slots.spp, slot_cap = slots.cap;
     const uint64_t win = std::max<uint64_t>(spd, window_bytes / seg / spd * spd);   // segments per window
     const int readers = (int)std::min<uint64_t>(64, env_bytes("DEOSS_FP_READERS", kFpReaders));
     RC_TRY(begin_call(c, d, s));
@@ -329,8 +169,6 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::stri
     for (auto& e : ev.slot) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&ev.rs, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&ev.copied, hipEventDisableTiming));
-    const std::string base = dir + "/.dm-fp-" + std::to_string((long long)::getpid()) + "-" +
-                             std::to_string((unsigned long long)g_fp_seq++) + "-";
     // where data files are copied from: the open file (kernel copies) or, for a pipe, its bytes
     const uint8_t* mem = fs.mem[0].empty() ? nullptr : fs.mem[0].data();
     int in_fd = fs.fd[0];
@@ -362,21 +200,8 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::stri
     auto start_data_files = [&](uint64_t w0, uint64_t ns) {
         std::vector<FpFile> files;
         for (uint64_t gs = w0; gs < w0 + ns; gs++) {
-            const bool padded = gs == tail_seg;
-            auto add = [&](uint64_t off_in_seg, uint64_t len, const std::string& tmp) {
-                if (padded) files.push_back({tail.data() + off_in_seg, len, tmp});
-                else if (mem) files.push_back({mem + gs * seg + off_in_seg, len, tmp});
-                else files.push_back({nullptr, len, tmp, in_fd, gs * seg + off_in_seg});
-            };
-            for (int j = 0; j < k; j++) {
-                const uint64_t id = gs * (uint64_t)total + (uint64_t)j;
-                add((uint64_t)j * frag, frag, base + "f" + std::to_string(id));
-                pend.emplace_back(files.back().tmp, 32 * id);
-            }
-            if (flags & DM_FP_SEGMENT_FILES) {
-                add(0, seg, base + "s" + std::to_string(gs));
-                pend.emplace_back(files.back().tmp, ~(32 * gs));   // ~: a segment digest
-            }
+            const uint8_t* src = gs == tail_seg ? tail.data() : mem ? mem + gs * seg : nullptr;
+            out.data_files(lay, gs, src, in_fd, gs * seg, (flags & DM_FP_SEGMENT_FILES) != 0, files);
         }
         wd.start(std::move(files), (size_t)env_bytes("DEOSS_FP_DATA_WRITERS", kFpDataWriters));
     };
@@ -443,7 +268,7 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::stri
             }
             // the data files need only the file: their copies run from the start, beside the reads
             start_data_files(w0, ns);
-            RC_TRY(fp_striped_pass(r, d, s, kit, fs, fbeg, fend, ns, seg, slot_cap, readers, take_slot, busy, ev,
+            RC_TRY(fp_striped_pass(r, d, s, kit, fs, fbeg, fend, ns, lay, slot_cap, readers, take_slot, busy, ev,
                                    parity, dfid, tr));
         }
         // C: while the leaf chains run, the parity comes back through the slots and is written as
@@ -459,25 +284,15 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::stri
             HIP_TRY(hipMemcpyAsync(buf, parity + t0 * pbytes, nt * pbytes, hipMemcpyDeviceToHost, d.copy));
             HIP_TRY(hipEventRecord(ev.slot[sl], d.copy));
             HIP_TRY(hipEventSynchronize(ev.slot[sl]));
-            std::vector<FpFile> files;
-            for (uint64_t u = 0; u < nt; u++) {
-                const uint64_t gs = w0 + t0 + u;
-                for (int i = 0; i < m; i++) {
-                    const uint64_t id = gs * (uint64_t)total + (uint64_t)(k + i);
-                    files.push_back({buf + u * pbytes + (uint64_t)i * frag, frag, base + "f" + std::to_string(id)});
-                    pend.emplace_back(files.back().tmp, 32 * id);
-                }
-            }
-            wr[sl].start(std::move(files));
+            wr[sl].start(out.parity_files(lay, w0 + t0, nt, buf));
             busy[sl] = true;
         }
         tr.mark("C: parity back, writes queued");
-        // D: digests.  One pass: d.leaves holds segment t at t, fragment (t, j) at ns + t * total + j.
-        // Striped: segment t at t, data fragment (t, q) at ns * (1 + q) + t, parity fragment (t, i)
-        // at ns * (1 + k) + t * m + i (interleaved here)
+        // D: digests.  One pass: d.leaves holds the segments, then the fragments (FpLayout::seg_slot,
+        // frag_slot), as segd / fragd do; the striped order is brought into that one here
         std::vector<uint8_t> lv;
         if (striped) {
-            lv.resize(32 * ns * (1 + (uint64_t)total));
+            lv.resize(32 * lay.leaves(ns));
             HIP_TRY(hipMemcpyAsync(lv.data(), d.leaves.p, lv.size(), hipMemcpyDeviceToHost, s));
         } else {
             HIP_TRY(hipMemcpyAsync(segd.data() + 32 * w0, d.leaves.p, 32 * ns, hipMemcpyDeviceToHost, s));
@@ -486,14 +301,7 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::stri
         }
         if (one_window) HIP_TRY(hipMemcpyAsync(fid, dfid, 32, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (striped) {
-            std::memcpy(segd.data() + 32 * w0, lv.data(), 32 * ns);
-            for (uint64_t t = 0; t < ns; t++)
-                for (int j = 0; j < total; j++) {
-                    const uint64_t from = j < k ? ns * (1 + (uint64_t)j) + t : ns * (1 + (uint64_t)k) + t * m + (j - k);
-                    std::memcpy(fragd.data() + 32 * ((w0 + t) * total + j), lv.data() + 32 * from, 32);
-                }
-        }
+        if (striped) lay.striped_to_one_pass(ns, lv.data(), segd.data() + 32 * w0, fragd.data() + 32 * w0 * total);
         HIP_TRY(hipStreamSynchronize(d.copy));   // this window's slots are in host memory: HBM reusable
         tr.mark("D: leaf pass done");
         const std::string e = wd.wait();
@@ -505,13 +313,8 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, const std::stri
         if (!e.empty()) return fail(c, DM_ERR_IO, "%s", e.c_str());
     }
     tr.mark("parity files written");
-    if (!one_window) {   // several windows: the fid is the tree over every segment digest
-        HIP_TRY(d.leaves.ensure(32 * nseg));
-        HIP_TRY(hipMemcpyAsync(d.leaves.p, segd.data(), 32 * nseg, hipMemcpyHostToDevice, s));
-        RC_TRY(finish(c, d, s, d.leaves.u8(), nseg, true, d.root.u8()));
-        HIP_TRY(hipMemcpyAsync(fid, d.root.p, 32, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
+    // several windows: the fid is the tree over every segment digest
+    if (!one_window) RC_TRY(rt_fid(c, d, s, segd.data(), nseg, fid));
     return DM_OK;
 }
 
@@ -536,15 +339,14 @@ int dm_full_processing(dm_rs* r, const char* path, const char* savedir, uint64_t
     if ((seg_hashes || frag_hashes) && cap < nseg)
         return fail(c, DM_ERR_INVALID, "dm_full_processing: %llu segments, digest arrays hold %llu",
                     (unsigned long long)nseg, (unsigned long long)cap);
-    std::string dir = savedir;
-    while (dir.size() > 1 && dir.back() == '/') dir.pop_back();
-    const std::string me = mkdir_all(dir);
+    FpOutputs out;
+    out.open(savedir, ".dm-fp-");
+    const std::string me = mkdir_all(out.dir);
     if (!me.empty()) return fail(c, DM_ERR_IO, "%s", me.c_str());
     const int total = r->k + r->m;
     std::vector<uint8_t> segd(32 * nseg), fragd(32 * nseg * total);
-    std::vector<std::pair<std::string, uint64_t>> pend;
     Dev& d = c->devs[g];
-    int rc = full_processing_windows(r, d, fs, dir, segment, flags, segd, fragd, pend, fid);
+    int rc = full_processing_windows(r, d, fs, out, segment, flags, segd, fragd, fid);
     {
         if (rc != DM_OK) {   // a failed call may leave copies queued: none may land in a slot the next call fills
             (void)hipStreamSynchronize(d.copy);
@@ -556,18 +358,12 @@ int dm_full_processing(dm_rs* r, const char* path, const char* savedir, uint64_t
         if (d.data.cap > kFpKeepBytes) c->reaper.put(d.id, d.data);
         if (rs_ln(r, d).work.cap > kFpKeepBytes) c->reaper.put(d.id, rs_ln(r, d).work);
     }
-    for (size_t i = 0; rc == DM_OK && i < pend.size(); i++) {
-        const uint64_t at = pend[i].second;
-        const uint8_t* dig = (at >> 63) ? segd.data() + ~at : fragd.data() + at;
-        const std::string to = dir + "/" + hex32(dig);
-        if (::rename(pend[i].first.c_str(), to.c_str()) != 0)
-            rc = fail(c, DM_ERR_IO, "rename %s %s: %s", pend[i].first.c_str(), to.c_str(), go_errno(errno).c_str());
-        else
-            pend[i].first.clear();
+    if (rc == DM_OK) {
+        const std::string e = out.rename_all(segd.data(), fragd.data());
+        if (!e.empty()) rc = fail(c, DM_ERR_IO, "%s", e.c_str());
     }
     if (rc != DM_OK) {   // no temporary survives a failed call
-        for (const auto& p : pend)
-            if (!p.first.empty()) ::unlink(p.first.c_str());
+        out.unlink_pending();
         return rc;
     }
     if (seg_hashes) std::memcpy(seg_hashes, segd.data(), segd.size());

@@ -30,12 +30,16 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "deoss_merkle.h"
 #include "merkle_kernels.hpp"
 #include "copy_pool.hpp"
 #include "shard_plan.hpp"
+#include "fp_files.hpp"
+
+using namespace dm_fp;   // fp_layout.hpp, fp_files.hpp: FullProcessing layout and output files (host only)
 
 namespace {
 
@@ -869,6 +873,30 @@ dm::LeafArgs uniform_args(const void* dev, uint64_t len, uint64_t chunk) {
     return la;
 }
 
+// Table-mode leaf arguments: leaf i is the lens[i] bytes at address addrs[i] (device tables).
+dm::LeafArgs table_args(const void* addrs, const void* lens, uint64_t n, uint8_t* digests) {
+    dm::LeafArgs la{};
+    la.addrs = static_cast<const uint64_t*>(addrs);
+    la.lens = static_cast<const uint64_t*>(lens);
+    la.nleaves = n;
+    la.byte_end = ~0ull;
+    la.digests = digests;
+    return la;
+}
+
+// The table twin of uniform_args, from host tables: starts the call's table uploads (the bounce
+// buffer holds these two tables and `extra` bytes of whatever the call uploads after them), uploads
+// addr and lens on s and fills *la; the digests go to d.leaves.
+int table_args(dm_ctx* c, Dev& d, hipStream_t s, const uint64_t* addr, const uint64_t* lens, uint64_t n,
+               uint64_t extra, dm::LeafArgs* la) {
+    RC_TRY(tables_begin(c, d, n * 16 + extra));
+    HIP_TRY(d.leaves.ensure(n * 32));
+    RC_TRY(upload(c, d, s, d.tab_addr, addr, n * 8));
+    RC_TRY(upload(c, d, s, d.tab_len, lens, n * 8));
+    *la = table_args(d.tab_addr.p, d.tab_len.p, n, d.leaves.u8());
+    return DM_OK;
+}
+
 // Finish: reduce n nodes to the root (>= 1 level if min_one or n > 1).
 int finish(dm_ctx* c, Dev& d, hipStream_t s, const uint8_t* nodes, uint64_t n, bool min_one, uint8_t* dst) {
     uint32_t D = ceil_log2(n);
@@ -924,16 +952,8 @@ int batch_device(dm_ctx* c, Dev& d, hipStream_t s, const void* const* objs, cons
             aligned &= (a & 15) == 0;
         }
     }
-    RC_TRY(tables_begin(c, d, T * 16 + (nobj + 1) * 12 + 1024));
-    HIP_TRY(d.leaves.ensure(T * 32));
-    RC_TRY(upload(c, d, s, d.tab_addr, addr.data(), T * 8));
-    RC_TRY(upload(c, d, s, d.tab_len, len.data(), T * 8));
-    dm::LeafArgs la{};
-    la.addrs = static_cast<const uint64_t*>(d.tab_addr.p);
-    la.lens = static_cast<const uint64_t*>(d.tab_len.p);
-    la.nleaves = T;
-    la.byte_end = ~0ull;
-    la.digests = d.leaves.u8();
+    dm::LeafArgs la;
+    RC_TRY(table_args(c, d, s, addr.data(), len.data(), T, (nobj + 1) * 12 + 1024, &la));
     hipEvent_t* tr = timing_record(c, d);
     if (tr) HIP_TRY(hipEventRecord(tr[0], s));
     RC_TRY(launch_leaves(c, d, s, la, true, aligned, kind >= 0 ? kind : pick_leaf_kernel(c, d, T)));
@@ -1486,16 +1506,8 @@ int chunks_leaves(dm_ctx* c, Dev& d, const void* const* ptrs, const uint64_t* le
     if (!zc) RC_TRY(pack_chunks(c, d, ptrs, lens, n, addr));
     bool aligned = true;
     for (uint64_t i = 0; i < n && zc; i++) aligned &= addr[i] % 16 == 0;
-    RC_TRY(tables_begin(c, d, n * 16 + 1024));
-    HIP_TRY(d.leaves.ensure(n * 32));
-    RC_TRY(upload(c, d, d.stream, d.tab_addr, addr.data(), n * 8));
-    RC_TRY(upload(c, d, d.stream, d.tab_len, lens, n * 8));
-    dm::LeafArgs la{};
-    la.addrs = static_cast<const uint64_t*>(d.tab_addr.p);
-    la.lens = static_cast<const uint64_t*>(d.tab_len.p);
-    la.nleaves = n;
-    la.byte_end = ~0ull;
-    la.digests = d.leaves.u8();
+    dm::LeafArgs la;
+    RC_TRY(table_args(c, d, d.stream, addr.data(), lens, n, 1024, &la));
     return launch_leaves(c, d, d.stream, la, true, aligned, zc ? DM_LEAF_QUAD : pick_leaf_kernel(c, d, n));
 }
 

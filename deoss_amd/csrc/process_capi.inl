@@ -19,49 +19,22 @@ namespace {
 // nseg segments at `obj` (segment-contiguous, padding already zeroed) belonging to objects whose
 // segments start at first[o] (first.size() == nobj + 1): RS coding, one leaf launch over every
 // segment and fragment, one fid per object into fids (nobj x 32, device).  Digests land in
-// d.leaves: segment s at s, fragment (s, j) at nseg + s * total + j.  after_rs (nullable) is
+// d.leaves in the one-pass order (FpLayout::seg_slot, frag_slot).  after_rs (nullable) is
 // recorded once the parity is written, so a caller can copy it out while the leaf kernel runs.
 int process_segments(dm_rs* r, Dev& d, hipStream_t s, uint8_t* obj, uint64_t segment, uint8_t* parity,
                      const std::vector<uint64_t>& first, uint8_t* fids, hipEvent_t after_rs = nullptr) {
     dm_ctx* c = r->c;
-    const int k = r->k, m = r->m, total = k + m;
-    const uint64_t nseg = first.back(), frag = segment / (uint64_t)k, nobj = first.size() - 1;
-    dm::RsArgs a{};
-    for (int j = 0; j < k; j++) a.in[j] = obj + (uint64_t)j * frag;
-    for (int i = 0; i < m; i++) a.out[i] = parity + (uint64_t)i * frag;
-    a.in_seg_stride = segment;
-    a.out_seg_stride = (uint64_t)m * frag;
-    a.units_per_seg = frag / 16;
-    a.nseg = nseg;
-    a.table = static_cast<const uint2*>(r->enc_tab.p);
-    a.nout = (uint32_t)m;
-    launch_rs(d, s, k, a);
-    HIP_TRY(hipGetLastError());
+    const FpLayout L(r->k, r->m, segment);
+    const uint64_t nseg = first.back(), nobj = first.size() - 1;
+    HIP_TRY(launch_rs(d, s, L.k, rs_encode_args(r, obj, L.seg, parity, L.pbytes, L.frag, nseg)));
     if (after_rs) HIP_TRY(hipEventRecord(after_rs, s));
     // leaf table: segments first (their chains are the longest: they start first), then fragments
-    const uint64_t T = nseg * (1 + (uint64_t)total);
+    const uint64_t T = L.leaves(nseg);
     std::vector<uint64_t> addr(T), lens(T);
-    for (uint64_t i = 0; i < nseg; i++) {
-        addr[i] = reinterpret_cast<uint64_t>(obj + i * segment);
-        lens[i] = segment;
-    }
-    for (uint64_t i = 0; i < nseg; i++)
-        for (int j = 0; j < total; j++) {
-            const uint64_t t = nseg + i * total + j;
-            addr[t] = reinterpret_cast<uint64_t>(j < k ? obj + i * segment + (uint64_t)j * frag
-                                                       : parity + (i * m + (j - k)) * frag);
-            lens[t] = frag;
-        }
-    RC_TRY(tables_begin(c, d, T * 16 + (nobj + 1) * 12 + 2048));
-    HIP_TRY(d.leaves.ensure(T * 32));
-    RC_TRY(upload(c, d, s, d.tab_addr, addr.data(), T * 8));
-    RC_TRY(upload(c, d, s, d.tab_len, lens.data(), T * 8));
-    dm::LeafArgs la{};
-    la.addrs = static_cast<const uint64_t*>(d.tab_addr.p);
-    la.lens = static_cast<const uint64_t*>(d.tab_len.p);
-    la.nleaves = T;
-    la.byte_end = ~0ull;
-    la.digests = d.leaves.u8();
+    const FpPiece all{obj, parity, nseg};
+    leaf_table(L, &all, 1, true, addr.data(), lens.data());
+    dm::LeafArgs la;
+    RC_TRY(table_args(c, d, s, addr.data(), lens.data(), T, (nobj + 1) * 12 + 2048, &la));
     hipEvent_t* tr = timing_record(c, d);
     if (tr) HIP_TRY(hipEventRecord(tr[0], s));
     RC_TRY(launch_leaves(c, d, s, la, true, true, pick_leaf_kernel(c, d, T)));
@@ -69,6 +42,18 @@ int process_segments(dm_rs* r, Dev& d, hipStream_t s, uint8_t* obj, uint64_t seg
     if (nobj == 1) RC_TRY(finish(c, d, s, d.leaves.u8(), nseg, true, fids));
     else RC_TRY(batch_roots_from_leaves(c, d, s, d.leaves.u8(), first, fids));
     if (tr) HIP_TRY(hipEventRecord(tr[2], s));
+    return DM_OK;
+}
+
+// The fid from segment digests held on the host (several windows, a stream's batches, a restore):
+// hashtree root over n digests -> root (host), in d's scratch; synchronises s.
+int rt_fid(dm_ctx* c, Dev& d, hipStream_t s, const uint8_t* segd, uint64_t n, uint8_t root[32]) {
+    HIP_TRY(d.leaves.ensure(32 * n));
+    HIP_TRY(d.root.ensure(32));
+    HIP_TRY(hipMemcpyAsync(d.leaves.p, segd, 32 * n, hipMemcpyHostToDevice, s));
+    RC_TRY(finish(c, d, s, d.leaves.u8(), n, true, d.root.u8()));
+    HIP_TRY(hipMemcpyAsync(root, d.root.p, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return DM_OK;
 }
 

@@ -20,7 +20,7 @@
 // reach the cap (DEOSS_PS_DEVICE_CAP, default kPsDeviceCap), write blocks: it launches the pending
 // batch early and waits for the oldest chunk to be reclaimable.
 // Results are those of dm_full_processing on the same bytes.  Part of merkle_capi.hip (after
-// fullproc_capi.inl: SlotWrites, write_whole, mkdir_all, hex32, env_bytes).
+// fullproc_capi.inl); layout and output files: fp_layout.hpp, fp_files.hpp.
 
 namespace {
 
@@ -54,9 +54,11 @@ struct PsBatch {
 struct dm_pstream {
     dm_rs* r = nullptr;
     StreamKit* kit = nullptr;   // pooled streams, events, pinned slots (borrowed for the stream's life)
-    int k = 0, m = 0, total = 0, flags = 0;
-    uint64_t seg = 0, frag = 0, pbytes = 0, spd = 1, spp = 1, slot_len = 0, batch_chunks = kPsBatchChunks;
-    std::string dir, base;
+    int flags = 0;
+    FpLayout lay;
+    FpSlots slots{1, 1, 0};
+    uint64_t slot_len = 0, batch_chunks = kPsBatchChunks;   // slot_len: the segments of a slot
+    FpOutputs out;
     PinnedBuf slot[kPsSlots];
     hipEvent_t ev_slot[kPsSlots] = {};
     SlotWrites wr[kPsSlots];
@@ -74,7 +76,6 @@ struct dm_pstream {
     uint64_t reclaimed_upto = 0;    // chunks [0, reclaimed_upto) gave their device buffer back
     std::vector<DevBuf> spare;      // reclaimed chunk buffers, reused by later chunks
     uint64_t dev_cap = kPsDeviceCap, dev_held = 0, dev_peak = 0;   // chunk buffers allocated (in use + spare)
-    std::vector<std::pair<std::string, uint64_t>> pend;   // temporary, digest index (~: segment)
     std::string err;
     int failed = DM_OK;   // sticky: after a failed write the stream only aborts (close returns this)
     Dev tree;             // the stream's own fid scratch: close takes no context lock
@@ -105,7 +106,7 @@ int ps_take_slot(dm_pstream* st, int* out) {
     do {   // never the slot being filled / flushed (a drain inside ps_flush must not reuse it)
         sl = (int)(st->next_slot++ % kPsSlots);
     } while (sl == st->cur);
-    PSHIP(pinned_grow(st->r->c, ps_dev(st).id, st->slot[sl], std::max(st->slot_len, st->spp * st->pbytes)));
+    PSHIP(pinned_grow(st->r->c, ps_dev(st).id, st->slot[sl], st->slots.cap));
     if (st->busy[sl]) {
         PSHIP(hipEventSynchronize(st->ev_slot[sl]));
         const std::string e = st->wr[sl].wait();
@@ -120,28 +121,18 @@ int ps_take_slot(dm_pstream* st, int* out) {
 int ps_drain_chunk(dm_pstream* st, uint64_t ci) {
     PsChunk* ch = st->chunks[ci];
     if (!ch->mem.p) return pfail(st, DM_ERR_INVALID, "pstream: draining a chunk without device memory");
-    uint8_t* parity = ch->mem.u8() + ch->ns * st->seg;
-    for (uint64_t t0 = 0; t0 < ch->ns; t0 += st->spp) {
-        const uint64_t nt = std::min(st->spp, ch->ns - t0);
+    uint8_t* parity = ch->mem.u8() + ch->ns * st->lay.seg;
+    for (uint64_t t0 = 0; t0 < ch->ns; t0 += st->slots.spp) {
+        const uint64_t nt = std::min(st->slots.spp, ch->ns - t0);
         int sl;
         int rc = ps_take_slot(st, &sl);
         if (rc != DM_OK) return rc;
         uint8_t* buf = st->slot[sl].u8();
         PSHIP(hipStreamWaitEvent(st->copy, ch->ev_rs, 0));
-        PSHIP(hipMemcpyAsync(buf, parity + t0 * st->pbytes, nt * st->pbytes, hipMemcpyDeviceToHost, st->copy));
+        PSHIP(hipMemcpyAsync(buf, parity + t0 * st->lay.pbytes, nt * st->lay.pbytes, hipMemcpyDeviceToHost, st->copy));
         PSHIP(hipEventRecord(st->ev_slot[sl], st->copy));
         PSHIP(hipEventSynchronize(st->ev_slot[sl]));
-        std::vector<FpFile> files;
-        for (uint64_t u = 0; u < nt; u++) {
-            const uint64_t gs = ch->s0 + t0 + u;
-            for (int i = 0; i < st->m; i++) {
-                const uint64_t id = gs * (uint64_t)st->total + (uint64_t)(st->k + i);
-                files.push_back({buf + u * st->pbytes + (uint64_t)i * st->frag, st->frag,
-                                 st->base + "f" + std::to_string(id)});
-                st->pend.emplace_back(files.back().tmp, 32 * id);
-            }
-        }
-        st->wr[sl].start(std::move(files));
+        st->wr[sl].start(st->out.parity_files(st->lay, ch->s0 + t0, nt, buf));
         st->busy[sl] = true;
     }
     ch->drained = true;
@@ -178,32 +169,18 @@ int ps_launch_batch(dm_pstream* st, uint64_t upto) {
             return pfail(st, DM_ERR_INVALID, "pstream: chunk without device memory in a leaf launch");
         b->ns += st->chunks[c]->ns;
     }
-    const uint64_t T = b->ns * (1 + (uint64_t)st->total);
+    const uint64_t T = st->lay.leaves(b->ns);
     uint8_t* htab = kit_table(st->r->c, d.id, st->kit, 16 * T);   // host side of the leaf table
     if (!htab) return pfail(st, DM_ERR_NOMEM, "pstream: pinned table arena");
     PSHIP(b->tab.ensure(16 * T));
     PSHIP(b->dig.ensure(32 * T));
     uint64_t* addr = reinterpret_cast<uint64_t*>(htab);
-    uint64_t* lens = addr + T;
-    uint64_t i = 0;
+    std::vector<FpPiece> pieces;   // a chunk: its segments, then their parity
     for (uint64_t c = b->c0; c < upto; c++) {
         PsChunk* ch = st->chunks[c];
-        for (uint64_t u = 0; u < ch->ns; u++, i++) {
-            addr[i] = reinterpret_cast<uint64_t>(ch->mem.u8() + u * st->seg);
-            lens[i] = st->seg;
-        }
+        pieces.push_back({ch->mem.u8(), ch->mem.u8() + ch->ns * st->lay.seg, ch->ns});
     }
-    for (uint64_t c = b->c0; c < upto; c++) {
-        PsChunk* ch = st->chunks[c];
-        const uint8_t* parity = ch->mem.u8() + ch->ns * st->seg;
-        for (uint64_t u = 0; u < ch->ns; u++)
-            for (int j = 0; j < st->total; j++, i++) {
-                addr[i] = reinterpret_cast<uint64_t>(
-                    j < st->k ? ch->mem.u8() + u * st->seg + (uint64_t)j * st->frag
-                              : parity + (u * st->m + (uint64_t)(j - st->k)) * st->frag);
-                lens[i] = st->frag;
-            }
-    }
+    leaf_table(st->lay, pieces.data(), pieces.size(), true, addr, addr + T);
     b->lane = (int)(st->batches.size() % 2);
     hipStream_t s = st->comp[b->lane];
     // after the RS launches of these chunks (in order on the code stream); batches on the two
@@ -211,12 +188,7 @@ int ps_launch_batch(dm_pstream* st, uint64_t upto) {
     PSHIP(hipEventRecord(st->ev_code, st->code));
     PSHIP(hipStreamWaitEvent(s, st->ev_code, 0));
     PSHIP(hipMemcpyAsync(b->tab.p, htab, 16 * T, hipMemcpyHostToDevice, s));
-    dm::LeafArgs la{};
-    la.addrs = static_cast<const uint64_t*>(b->tab.p);
-    la.lens = la.addrs + T;
-    la.nleaves = T;
-    la.byte_end = ~0ull;
-    la.digests = b->dig.u8();
+    const dm::LeafArgs la = table_args(b->tab.p, static_cast<const uint64_t*>(b->tab.p) + T, T, b->dig.u8());
     launch_leaves_t<true, true>(s, la, pick_leaf_kernel(st->r->c, d, T), d.cus);
     PSHIP(hipGetLastError());
     PSHIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
@@ -290,13 +262,13 @@ int ps_flush(dm_pstream* st) {
     if (st->cur < 0 || st->fill == 0) return DM_OK;
     Dev& d = ps_dev(st);
     const int sl = st->cur;
-    const uint64_t ns = ceil_div(st->fill, st->seg), len = ns * st->seg;
+    const uint64_t ns = ceil_div(st->fill, st->lay.seg), len = ns * st->lay.seg;
     uint8_t* buf = st->slot[sl].u8();
     if (len > st->fill) std::memset(buf + st->fill, 0, len - st->fill);
     // the buffer first: reclaiming may launch and drain every chunk already in the list, and a
     // chunk joins the list only once it has memory (its H2D and RS follow right below)
     DevBuf mem;
-    RC_TRY(ps_chunk_buffer(st, ns * (st->seg + st->pbytes), &mem));
+    RC_TRY(ps_chunk_buffer(st, ns * (st->lay.seg + st->lay.pbytes), &mem));
     PsChunk* ch = new PsChunk();
     ch->mem = mem;
     ch->s0 = st->chunks.empty() ? 0 : st->chunks.back()->s0 + st->chunks.back()->ns;
@@ -306,18 +278,8 @@ int ps_flush(dm_pstream* st) {
     PSHIP(hipMemcpyAsync(ch->mem.p, buf, len, hipMemcpyHostToDevice, st->copy));
     PSHIP(hipEventRecord(st->ev_slot[sl], st->copy));
     std::vector<FpFile> files;
-    for (uint64_t u = 0; u < ns; u++) {
-        const uint64_t gs = ch->s0 + u;
-        for (int j = 0; j < st->k; j++) {
-            const uint64_t id = gs * (uint64_t)st->total + (uint64_t)j;
-            files.push_back({buf + u * st->seg + (uint64_t)j * st->frag, st->frag, st->base + "f" + std::to_string(id)});
-            st->pend.emplace_back(files.back().tmp, 32 * id);
-        }
-        if (st->flags & DM_FP_SEGMENT_FILES) {
-            files.push_back({buf + u * st->seg, st->seg, st->base + "s" + std::to_string(gs)});
-            st->pend.emplace_back(files.back().tmp, ~(32 * gs));
-        }
-    }
+    for (uint64_t u = 0; u < ns; u++)
+        st->out.data_files(st->lay, ch->s0 + u, buf + u * st->lay.seg, -1, 0, (st->flags & DM_FP_SEGMENT_FILES) != 0, files);
     st->wr[sl].start(std::move(files));
     st->busy[sl] = true;
     st->cur = -1;
@@ -326,18 +288,8 @@ int ps_flush(dm_pstream* st) {
     hipStream_t s = st->code;
     PSHIP(hipEventRecord(st->ev_copy, st->copy));
     PSHIP(hipStreamWaitEvent(s, st->ev_copy, 0));
-    dm::RsArgs a{};
-    for (int j = 0; j < st->k; j++) a.in[j] = ch->mem.u8() + (uint64_t)j * st->frag;
-    uint8_t* parity = ch->mem.u8() + len;
-    for (int i = 0; i < st->m; i++) a.out[i] = parity + (uint64_t)i * st->frag;
-    a.in_seg_stride = st->seg;
-    a.out_seg_stride = st->pbytes;
-    a.units_per_seg = st->frag / 16;
-    a.nseg = ns;
-    a.table = static_cast<const uint2*>(st->r->enc_tab.p);
-    a.nout = (uint32_t)st->m;
-    launch_rs(d, s, st->k, a);
-    PSHIP(hipGetLastError());
+    PSHIP(launch_rs(d, s, st->lay.k, rs_encode_args(st->r, ch->mem.u8(), st->lay.seg, ch->mem.u8() + len, st->lay.pbytes,
+                                                    st->lay.frag, ns)));
     PSHIP(hipEventRecord(ch->ev_rs, s));
     if (st->chunks.size() - st->hashed_chunks >= st->batch_chunks) return ps_launch_batch(st, st->chunks.size());
     return DM_OK;
@@ -378,11 +330,6 @@ void ps_free(dm_pstream* st) {
     delete st;
 }
 
-void ps_unlink_pending(dm_pstream* st) {
-    for (const auto& p : st->pend)
-        if (!p.first.empty()) ::unlink(p.first.c_str());
-}
-
 int pstream_write(dm_pstream* st, const void* data, uint64_t len);
 int pstream_close(dm_pstream* st, uint8_t* seg_hashes, uint8_t* frag_hashes, uint64_t cap, uint64_t* nseg_out,
                   uint8_t fid[32]);
@@ -402,27 +349,17 @@ int dm_pstream_open(dm_rs* r, uint64_t segment, const char* savedir, int flags, 
     DeviceRestore dev;
     dm_pstream* st = new dm_pstream();
     st->r = r;
-    st->k = r->k;
-    st->m = r->m;
-    st->total = r->k + r->m;
     st->flags = flags;
-    st->seg = segment;
-    st->frag = segment / (uint64_t)r->k;
-    st->pbytes = (uint64_t)r->m * st->frag;
+    st->lay = FpLayout(r->k, r->m, segment);
     // test hooks (env, read at open): small slots / batches exercise slot reuse and many launches
-    const uint64_t slot_bytes = env_bytes("DEOSS_FP_SLOT_BYTES", kPsSlotBytes);
+    st->slots = fp_slots(st->lay, env_bytes("DEOSS_FP_SLOT_BYTES", kPsSlotBytes));
     st->batch_chunks = env_bytes("DEOSS_PS_BATCH_CHUNKS", kPsBatchChunks);
     st->dev_cap = env_bytes("DEOSS_PS_DEVICE_CAP", kPsDeviceCap);
-    st->spd = std::max<uint64_t>(1, slot_bytes / segment);
-    st->spp = std::max<uint64_t>(1, slot_bytes / st->pbytes);
-    st->slot_len = st->spd * segment;
-    st->dir = savedir;
-    while (st->dir.size() > 1 && st->dir.back() == '/') st->dir.pop_back();
-    st->base = st->dir + "/.dm-ps-" + std::to_string((long long)::getpid()) + "-" +
-               std::to_string((unsigned long long)g_fp_seq++) + "-";
+    st->slot_len = st->slots.spd * segment;
+    st->out.open(savedir, ".dm-ps-");
     int rc = DM_OK;
     do {
-        const std::string me = mkdir_all(st->dir);
+        const std::string me = mkdir_all(st->out.dir);
         if (!me.empty()) { rc = pfail(st, DM_ERR_IO, me); break; }
         if (hipSetDevice(ps_dev(st).id) != hipSuccess) { rc = pfail(st, DM_ERR_HIP, "hipSetDevice"); break; }
         if ((rc = kit_acquire(c, 0, &st->kit)) != DM_OK) {
@@ -509,7 +446,7 @@ int pstream_close(dm_pstream* st, uint8_t* seg_hashes, uint8_t* frag_hashes, uin
                   uint8_t fid[32]) {
     DeviceRestore dev;
     dm_ctx* c = st->r->c;
-    const uint64_t nseg = ceil_div(st->received, st->seg);
+    const uint64_t nseg = ceil_div(st->received, st->lay.seg);
     if (nseg_out) *nseg_out = nseg;
     int rc = DM_OK;
     do {
@@ -525,13 +462,13 @@ int pstream_close(dm_pstream* st, uint8_t* seg_hashes, uint8_t* frag_hashes, uin
         if ((rc = ps_launch_batch(st, st->chunks.size())) != DM_OK) break;
         if ((rc = ps_drain(st, true)) != DM_OK) break;
         // digests: batch b holds its ns segments, then ns x total fragments
-        std::vector<uint8_t> segd(32 * nseg), fragd(32 * nseg * st->total);
+        std::vector<uint8_t> segd(32 * nseg), fragd(32 * nseg * st->lay.total);
         for (PsBatch* b : st->batches) {
             hipStream_t s = st->comp[b->lane];
             hipError_t e;
             if ((e = hipMemcpyAsync(segd.data() + 32 * b->s0, b->dig.p, 32 * b->ns, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-                (e = hipMemcpyAsync(fragd.data() + 32 * b->s0 * st->total, b->dig.u8() + 32 * b->ns,
-                                    32 * b->ns * st->total, hipMemcpyDeviceToHost, s)) != hipSuccess) {
+                (e = hipMemcpyAsync(fragd.data() + 32 * b->s0 * st->lay.total, b->dig.u8() + 32 * b->ns,
+                                    32 * b->ns * st->lay.total, hipMemcpyDeviceToHost, s)) != hipSuccess) {
                 rc = pfail(st, DM_ERR_HIP, std::string("digests: ") + hipGetErrorString(e));
                 break;
             }
@@ -550,38 +487,20 @@ int pstream_close(dm_pstream* st, uint8_t* seg_hashes, uint8_t* frag_hashes, uin
             Dev& d = st->tree;
             d.id = ps_dev(st).id;
             d.cus = ps_dev(st).cus;
-            hipStream_t s = st->code;
-            hipError_t e;
-            if ((e = d.root.ensure(32)) != hipSuccess || (e = d.leaves.ensure(32 * nseg)) != hipSuccess ||
-                (e = hipMemcpyAsync(d.leaves.p, segd.data(), 32 * nseg, hipMemcpyHostToDevice, s)) != hipSuccess) {
-                rc = pfail(st, DM_ERR_HIP, std::string("fid: ") + hipGetErrorString(e));
-                break;
-            }
-            if ((rc = finish(c, d, s, d.leaves.u8(), nseg, true, d.root.u8())) != DM_OK) break;
-            if ((e = hipMemcpyAsync(fid, d.root.p, 32, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-                (e = hipStreamSynchronize(s)) != hipSuccess) {
-                rc = pfail(st, DM_ERR_HIP, std::string("fid: ") + hipGetErrorString(e));
+            if ((rc = rt_fid(c, d, st->code, segd.data(), nseg, fid)) != DM_OK) {
+                st->err = t_err;
                 break;
             }
         }
-        for (auto& p : st->pend) {
-            const uint64_t at = p.second;
-            const uint8_t* dig = (at >> 63) ? segd.data() + ~at : fragd.data() + at;
-            const std::string to = st->dir + "/" + hex32(dig);
-            if (::rename(p.first.c_str(), to.c_str()) != 0) {
-                rc = pfail(st, DM_ERR_IO, "rename " + p.first + " " + to + ": " + go_errno(errno));
-                break;
-            }
-            p.first.clear();
-        }
-        if (rc != DM_OK) break;
+        const std::string e = st->out.rename_all(segd.data(), fragd.data());
+        if (!e.empty()) { rc = pfail(st, DM_ERR_IO, e); break; }
         if (seg_hashes) std::memcpy(seg_hashes, segd.data(), segd.size());
         if (frag_hashes) std::memcpy(frag_hashes, fragd.data(), fragd.size());
     } while (0);
     if (rc != DM_OK) {
         t_err = st->err.empty() ? t_err : st->err;
         for (auto& w : st->wr) (void)w.wait();
-        ps_unlink_pending(st);
+        st->out.unlink_pending();
     }
     ps_free(st);
     return rc;
@@ -602,7 +521,7 @@ void dm_pstream_abort(dm_pstream* st) {
     if (!st) return;
     DeviceRestore dev;
     for (auto& w : st->wr) (void)w.wait();
-    ps_unlink_pending(st);
+    st->out.unlink_pending();
     ps_free(st);
 }
 

@@ -121,16 +121,7 @@ int restore_launch(dm_rs* r, Dev& d, hipStream_t s, const RestoreBatch& b, uint6
     a.units_per_seg = units;
     a.nseg = b.desc.size();
     const dim3 grid = rs_grid(d, units, a.nseg), block(dm::kRsThreads);
-    switch (r->k) {
-        case 1: hipLaunchKernelGGL(dm::rs_restore_kernel<1>, grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(dm::rs_restore_kernel<2>, grid, block, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(dm::rs_restore_kernel<3>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(dm::rs_restore_kernel<4>, grid, block, 0, s, a); break;
-        case 5: hipLaunchKernelGGL(dm::rs_restore_kernel<5>, grid, block, 0, s, a); break;
-        case 6: hipLaunchKernelGGL(dm::rs_restore_kernel<6>, grid, block, 0, s, a); break;
-        case 7: hipLaunchKernelGGL(dm::rs_restore_kernel<7>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(dm::rs_restore_kernel<8>, grid, block, 0, s, a); break;
-    }
+    rs_for_k(r->k, [&](auto K) { hipLaunchKernelGGL(dm::rs_restore_kernel<decltype(K)::value>, grid, block, 0, s, a); });
     HIP_TRY(hipGetLastError());
     return DM_OK;
 }
@@ -143,29 +134,10 @@ int rt_hash(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<uint64_t>& addrs
     dig.resize(32 * T);
     if (T == 0) return DM_OK;
     const std::vector<uint64_t> lens(T, len);
-    RC_TRY(tables_begin(c, d, T * 16 + 1024));
-    HIP_TRY(d.leaves.ensure(T * 32));
-    RC_TRY(upload(c, d, s, d.tab_addr, addrs.data(), T * 8));
-    RC_TRY(upload(c, d, s, d.tab_len, lens.data(), T * 8));
-    dm::LeafArgs la{};
-    la.addrs = static_cast<const uint64_t*>(d.tab_addr.p);
-    la.lens = static_cast<const uint64_t*>(d.tab_len.p);
-    la.nleaves = T;
-    la.byte_end = ~0ull;
-    la.digests = d.leaves.u8();
+    dm::LeafArgs la;
+    RC_TRY(table_args(c, d, s, addrs.data(), lens.data(), T, 1024, &la));
     RC_TRY(launch_leaves(c, d, s, la, true, true, pick_leaf_kernel(c, d, T)));
     HIP_TRY(hipMemcpyAsync(dig.data(), d.leaves.p, 32 * T, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return DM_OK;
-}
-
-// hashtree root over n segment digests (host) -> root (host); synchronises s.
-int rt_fid(dm_ctx* c, Dev& d, hipStream_t s, const uint8_t* segd, uint64_t n, uint8_t root[32]) {
-    HIP_TRY(d.leaves.ensure(32 * n));
-    HIP_TRY(d.root.ensure(32));
-    HIP_TRY(hipMemcpyAsync(d.leaves.p, segd, 32 * n, hipMemcpyHostToDevice, s));
-    RC_TRY(finish(c, d, s, d.leaves.u8(), n, true, d.root.u8()));
-    HIP_TRY(hipMemcpyAsync(root, d.root.p, 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return DM_OK;
 }
@@ -357,8 +329,9 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
     RsLane& L = rs_ln(r, d);
     hipStream_t s = d.stream;
     RC_TRY(begin_call(c, d, s));
-    const int k = r->k, m = r->m, total = k + m;
-    const uint64_t frag = segment / (uint64_t)k;
+    const FpLayout lay(r->k, r->m, segment);   // parity fragments in L.work, laid out as FullProcessing's
+    const int k = lay.k, total = lay.total;
+    const uint64_t frag = lay.frag;
     // test hooks (env, read per call): small windows and slots exercise several windows and slot reuse
     const uint64_t win = std::max<uint64_t>(1, env_bytes("DEOSS_RT_WINDOW_BYTES", kRtWindowBytes) / segment);
     const uint64_t slot_cap = std::max(env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes), frag);
@@ -374,7 +347,7 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
         const uint64_t ns = std::min(win, nseg - w0), NF = ns * (uint64_t)total;
         HIP_TRY(hipStreamSynchronize(s));   // the previous window's kernels are done with the object buffer
         HIP_TRY(d.data.ensure(ns * segment + kAlign));
-        HIP_TRY(L.work.ensure(ns * (uint64_t)m * frag + 16));
+        HIP_TRY(L.work.ensure(ns * lay.pbytes + 16));
         std::vector<const uint8_t*> dev(NF, nullptr);
         std::vector<uint8_t> good(NF, 0);
         std::vector<int> cand(ns, 0), ngood(ns, 0);
@@ -397,9 +370,7 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
                         wf[i] = kFragBad;   // not a fragment of this object's shape
                         continue;
                     }
-                    uint8_t* to = j < k ? d.data.u8() + t * segment + (uint64_t)j * frag
-                                        : L.work.u8() + (t * (uint64_t)m + (uint64_t)(j - k)) * frag;
-                    loads.push_back({i, p, to});
+                    loads.push_back({i, p, lay.frag_ptr(d.data.u8(), L.work.u8(), t, j)});
                     need--;
                 }
             }

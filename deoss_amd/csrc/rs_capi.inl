@@ -144,18 +144,43 @@ dim3 rs_grid(const Dev& d, uint64_t units, uint64_t nseg) {
     return dim3(gx, gy);
 }
 
-void launch_rs(Dev& d, hipStream_t s, int k, const dm::RsArgs& a) {
-    const dim3 grid = rs_grid(d, a.units_per_seg, a.nseg), block(dm::kRsThreads);
+// f(std::integral_constant<int, K>()) for K = k: the rs kernels take the data shard count as a
+// template argument (1 .. kRsMaxIn, checked by dm_rs_create).
+template <class F>
+void rs_for_k(int k, F&& f) {
+    static_assert(dm::kRsMaxIn == 8, "one case per data shard count");
     switch (k) {
-        case 1: hipLaunchKernelGGL(dm::rs_code_kernel<1>, grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(dm::rs_code_kernel<2>, grid, block, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(dm::rs_code_kernel<3>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(dm::rs_code_kernel<4>, grid, block, 0, s, a); break;
-        case 5: hipLaunchKernelGGL(dm::rs_code_kernel<5>, grid, block, 0, s, a); break;
-        case 6: hipLaunchKernelGGL(dm::rs_code_kernel<6>, grid, block, 0, s, a); break;
-        case 7: hipLaunchKernelGGL(dm::rs_code_kernel<7>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(dm::rs_code_kernel<8>, grid, block, 0, s, a); break;
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: f(std::integral_constant<int, 5>()); break;
+        case 6: f(std::integral_constant<int, 6>()); break;
+        case 7: f(std::integral_constant<int, 7>()); break;
+        default: f(std::integral_constant<int, 8>()); break;
     }
+}
+
+hipError_t launch_rs(Dev& d, hipStream_t s, int k, const dm::RsArgs& a) {
+    const dim3 grid = rs_grid(d, a.units_per_seg, a.nseg), block(dm::kRsThreads);
+    rs_for_k(k, [&](auto K) { hipLaunchKernelGGL(dm::rs_code_kernel<decltype(K)::value>, grid, block, 0, s, a); });
+    return hipGetLastError();
+}
+
+// Encode arguments for nseg segments: data shard j of segment t at data + t * data_stride +
+// j * shard, parity shard i at parity + t * parity_stride + i * shard (r's parity rows).
+dm::RsArgs rs_encode_args(const dm_rs* r, const uint8_t* data, uint64_t data_stride, uint8_t* parity,
+                          uint64_t parity_stride, uint64_t shard, uint64_t nseg) {
+    dm::RsArgs a{};
+    for (int j = 0; j < r->k; j++) a.in[j] = data + (uint64_t)j * shard;
+    for (int i = 0; i < r->m; i++) a.out[i] = parity + (uint64_t)i * shard;
+    a.in_seg_stride = data_stride;
+    a.out_seg_stride = parity_stride;
+    a.units_per_seg = shard / 16;
+    a.nseg = nseg;
+    a.table = static_cast<const uint2*>(r->enc_tab.p);
+    a.nout = (uint32_t)r->m;
+    return a;
 }
 
 // Coding rows that rebuild the missing shards from the first k present ones (klauspost
@@ -209,8 +234,7 @@ int rs_reconstruct_dev(dm_rs* r, Dev& d, hipStream_t s, uint8_t* const* shards, 
     a.nseg = 1;
     a.table = static_cast<const uint2*>(L.dec_tab.p);
     a.nout = (uint32_t)nmiss;
-    launch_rs(d, s, r->k, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_rs(d, s, r->k, a));
     return DM_OK;
 }
 
@@ -297,19 +321,11 @@ int dm_rs_encode_device_async(dm_rs* r, const void* data, uint64_t data_stride, 
     Dev& d = c->devs[g];
     hipStream_t s = pick_stream(d, stream);
     RC_TRY(begin_call(c, d, s));
-    dm::RsArgs a{};
-    for (int j = 0; j < r->k; j++) a.in[j] = static_cast<const uint8_t*>(data) + (uint64_t)j * shard;
-    for (int i = 0; i < r->m; i++) a.out[i] = static_cast<uint8_t*>(parity) + (uint64_t)i * shard;
-    a.in_seg_stride = data_stride;
-    a.out_seg_stride = parity_stride;
-    a.units_per_seg = shard / 16;
-    a.nseg = nseg;
-    a.table = static_cast<const uint2*>(r->enc_tab.p);
-    a.nout = (uint32_t)r->m;
+    const dm::RsArgs a = rs_encode_args(r, static_cast<const uint8_t*>(data), data_stride, static_cast<uint8_t*>(parity),
+                                        parity_stride, shard, nseg);
     hipEvent_t* tr = timing_record(c, d);
     if (tr) HIP_TRY(hipEventRecord(tr[0], s));
-    launch_rs(d, s, r->k, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_rs(d, s, r->k, a));
     if (tr) {
         HIP_TRY(hipEventRecord(tr[1], s));
         HIP_TRY(hipEventRecord(tr[2], s));
@@ -355,16 +371,7 @@ int dm_rs_encode(dm_rs* r, const void* const* data, void* const* parity, uint64_
     HIP_TRY(work.ensure(pitch * total));
     for (int j = 0; j < r->k; j++)
         HIP_TRY(hipMemcpyAsync(work.u8() + j * pitch, data[j], shard, hipMemcpyHostToDevice, s));
-    dm::RsArgs a{};
-    for (int j = 0; j < r->k; j++) a.in[j] = work.u8() + j * pitch;
-    for (int i = 0; i < r->m; i++) a.out[i] = work.u8() + (r->k + i) * pitch;
-    a.in_seg_stride = a.out_seg_stride = 0;
-    a.units_per_seg = pitch / 16;
-    a.nseg = 1;
-    a.table = static_cast<const uint2*>(r->enc_tab.p);
-    a.nout = (uint32_t)r->m;
-    launch_rs(d, s, r->k, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_rs(d, s, r->k, rs_encode_args(r, work.u8(), 0, work.u8() + r->k * pitch, 0, pitch, 1)));
     for (int i = 0; i < r->m; i++)
         HIP_TRY(hipMemcpyAsync(parity[i], work.u8() + (r->k + i) * pitch, shard, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -62,16 +62,8 @@ int verify_dev(dm_ctx* c, Dev& d, hipStream_t s, const void* const* contents, co
         len[t] = lens[t];
         aligned &= (addr[t] & 15) == 0;
     }
-    RC_TRY(tables_begin(c, d, q * 16 + 1024));
-    HIP_TRY(d.leaves.ensure(q * 32));
-    RC_TRY(upload(c, d, s, d.tab_addr, addr.data(), q * 8));
-    RC_TRY(upload(c, d, s, d.tab_len, len.data(), q * 8));
-    dm::LeafArgs la{};
-    la.addrs = static_cast<const uint64_t*>(d.tab_addr.p);
-    la.lens = static_cast<const uint64_t*>(d.tab_len.p);
-    la.nleaves = q;
-    la.byte_end = ~0ull;
-    la.digests = d.leaves.u8();
+    dm::LeafArgs la;
+    RC_TRY(table_args(c, d, s, addr.data(), len.data(), q, 1024, &la));
     RC_TRY(launch_leaves(c, d, s, la, true, aligned, pick_leaf_kernel(c, d, q)));
     hipLaunchKernelGGL(dm::verify_kernel, dim3((uint32_t)ceil_div(q, dm::kProofBlock)), dim3(dm::kProofBlock), 0, s,
                        d.leaves.u8(), paths, bits, depth, q, roots, root_stride, ok);
