@@ -10,6 +10,7 @@
 // 32-byte big-endian SHA-256 output (what Go's h.Sum(nil) returns).  Inside a kernel nodes
 // live as 8 state words (byte swapped once at load / store).
 #pragma once
+#include "quad_ring.hpp"
 #include "sha256_gfx950.hpp"
 
 namespace dm {
@@ -599,8 +600,9 @@ constexpr int kQuadLeaves = 8;      // leaves per workgroup (8 consumer lanes pe
 constexpr int kQuadBlocks = 8;      // blocks per leaf per ring stage (one producer lane each)
 constexpr int kQuadFuseMax = 3;     // 8 leaves -> 1 node
 // Two LDS footprints (template COMPACT), one ring layout: -(K+W) [stage][group][block][leaf].
-// Wide reserves a second, unused 32 KiB region so that at most two workgroups share a CU and the
-// dispatcher spreads them; compact (33 KiB, four per CU) is used for 4,097 .. 8,192 leaves.  The
+// Wide has 64 KiB (a ring of three stages and 16 KiB unused; it was two stages and a second,
+// unused 32 KiB region) so that at most two workgroups share a CU and the dispatcher spreads
+// them; compact (33 KiB, four per CU, two stages) is used for 4,097 .. 8,192 leaves.  The
 // lock-step K1Q needed a region of ones for its a-triple (wide) or one broadcast ones entry per
 // row (compact, 9-entry rows); the skewed step needs neither.
 constexpr int kQuadRow = kQuadLeaves;
@@ -883,6 +885,100 @@ __device__ __forceinline__ void quad_stage_regs(uint32_t (&x)[4], const uint4* k
     quad_stage_blocks<G, ROW, MIS>(x, P, h, g, S, kw, sh, msk);
 }
 
+// The wide kernel's run of n >= 1 whole stages as ONE step stream (schedule: quad_ring.hpp).  Its
+// ring is three stages deep, so stage it + 1 is complete while the consumer runs stage it: the
+// boundary between two stages of a run is a DM_QS_LINKQ like the 7 inside a stage, and blocks 6
+// and 7 load the words of the next stage's blocks 0 and 1, so the stream fills once at the run's
+// first block and drains once at its last, and no LDS latency is exposed at a stage boundary
+// (a stage that drained at its barrier issued its first 8 ds_read_b128 after the barrier and
+// waited for them at once).  Four register sets: 8 = 0 mod 4 keeps every index static.
+//   FILL / TAIL: the stream's first / last block.  LOAD: load block K8 + 2's words from src (the
+//   ring column of the stage that block belongs to; the run's last stage loads nothing beyond itself).
+constexpr int kQuadWideRing = quad_ring::kWideDepth;
+constexpr int kQuadSets = quad_ring::kSets;
+template <int G, int ROW, int K8, bool FILL, bool TAIL, bool LOAD>
+__device__ __forceinline__ void quad_xstage_block(uint32_t (&x)[4], uint32_t (&P)[4], uint32_t& h, uint32_t& g,
+                                                  uint4 (&S)[kQuadSets][4], const uint4* src, uint3 sh, uint32_t msk) {
+    static_assert((LOAD || !quad_ring::block_prefetches(K8, true)) && (!TAIL || !quad_ring::block_links(K8, true)) &&
+                      !(FILL && TAIL) && quad_ring::prefetch_of(K8).block == (K8 + quad_ring::kAhead) % kQuadBlocks,
+                  "only the last stage of a run skips a load or drains: quad_ring.hpp");
+    __builtin_amdgcn_s_waitcnt(kLgkmWait0);
+    if constexpr (LOAD) {
+        constexpr quad_ring::BlockRef pf = quad_ring::prefetch_of(K8);
+#pragma unroll
+        for (int t = 0; t < 4; t++) S[quad_ring::set_of(K8 + quad_ring::kAhead)][t] = src[pf.block * ROW + 4 * t * G];
+    }
+    quad_block_regs<false, FILL ? 0 : TAIL ? kQuadBlocks - 1 : 1>(x, P, h, g, S[quad_ring::set_of(K8)],
+                                                                 S[quad_ring::set_of(K8 + 1)][0], sh, msk);
+}
+// colp: this lane's column of ring slot 0; slot: the slot of the run's first stage.  Returns the
+// slot of the stage after the run.  One barrier per stage, after its block 7; the loop body is
+// blocks 1..7 of a stage, the barrier, and block 0 of the next, so that one copy of a block 0
+// (the fill) and one of blocks 1..7 (the drain) are all the code outside the loop.
+template <int G, int ROW>
+__device__ __forceinline__ uint32_t quad_run_xstage(uint32_t (&x)[4], const uint4* colp, uint32_t slot, uint64_t n,
+                                                    uint3 sh, uint32_t msk) {
+    uint4 S[kQuadSets][4];
+    uint32_t P[4] = {x[0], x[1], x[2], x[3]}, h, g;
+    const uint4* cur = colp + slot * 16 * G;
+#pragma unroll
+    for (int k = 0; k < quad_ring::kAhead; k++) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) S[k][t] = cur[k * ROW + 4 * t * G];
+    }
+    quad_xstage_block<G, ROW, 0, true, false, true>(x, P, h, g, S, cur, sh, msk);
+    for (uint64_t s = 1; s < n; s++) {
+        slot = quad_ring::next_slot(slot, kQuadWideRing);
+        const uint4* nxt = colp + slot * 16 * G;
+        quad_xstage_block<G, ROW, 1, false, false, true>(x, P, h, g, S, cur, sh, msk);
+        quad_xstage_block<G, ROW, 2, false, false, true>(x, P, h, g, S, cur, sh, msk);
+        quad_xstage_block<G, ROW, 3, false, false, true>(x, P, h, g, S, cur, sh, msk);
+        quad_xstage_block<G, ROW, 4, false, false, true>(x, P, h, g, S, cur, sh, msk);
+        quad_xstage_block<G, ROW, 5, false, false, true>(x, P, h, g, S, cur, sh, msk);
+        quad_xstage_block<G, ROW, 6, false, false, true>(x, P, h, g, S, nxt, sh, msk);
+        quad_xstage_block<G, ROW, 7, false, false, true>(x, P, h, g, S, nxt, sh, msk);
+        __syncthreads();   // stage done  /  the stage after next full
+        quad_xstage_block<G, ROW, 0, false, false, true>(x, P, h, g, S, nxt, sh, msk);
+        cur = nxt;
+    }
+    quad_xstage_block<G, ROW, 1, false, false, true>(x, P, h, g, S, cur, sh, msk);
+    quad_xstage_block<G, ROW, 2, false, false, true>(x, P, h, g, S, cur, sh, msk);
+    quad_xstage_block<G, ROW, 3, false, false, true>(x, P, h, g, S, cur, sh, msk);
+    quad_xstage_block<G, ROW, 4, false, false, true>(x, P, h, g, S, cur, sh, msk);
+    quad_xstage_block<G, ROW, 5, false, false, true>(x, P, h, g, S, cur, sh, msk);
+    quad_xstage_block<G, ROW, 6, false, false, false>(x, P, h, g, S, cur, sh, msk);
+    quad_xstage_block<G, ROW, 7, false, true, false>(x, P, h, g, S, cur, sh, msk);
+    __syncthreads();
+    return quad_ring::next_slot(slot, kQuadWideRing);
+}
+
+// K1Q's producer step: block b of this lane's leaf (nothing beyond the leaf's end) as -(K+W)
+// into its ring stage at kw, and the load of the lane's next block (b + 8) into cur.
+template <bool ALIGNED, int G>
+__device__ __forceinline__ void quad_produce_block(const LeafView& v, Blk& cur, uint64_t b, uint4* kw) {
+    if (b >= v.nb) return;
+    uint32_t w[16];
+    block_words(cur, w);
+    if (b + kQuadBlocks < v.nb) cur = load_block<ALIGNED>(v.p + 64 * (b + kQuadBlocks));
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        uint32_t u[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int t = 4 * q + k;
+            uint32_t wt;
+            if (t < 16) {
+                wt = w[t];
+            } else {
+                wt = ssig1(w[(t - 2) & 15]) + w[(t - 7) & 15] + ssig0(w[(t - 15) & 15]) + w[t & 15];
+                w[t & 15] = wt;
+            }
+            u[k] = 0u - (kSha256K[t] + wt);   // the consumer subtracts it
+        }
+        kw[q * G] = make_uint4(u[0], u[1], u[2], u[3]);
+    }
+}
+
 template <bool TABLE, bool ALIGNED, bool COMPACT>
 __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
     constexpr int ROW = COMPACT ? kQuadRow : kQuadLeaves;     // uint4 per (group, block) row
@@ -890,10 +986,16 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
     // -(K+W) [stage][group][block][leaf (compact: + one unused entry)].  The wide layout reserves a
     // second, unused region: 64 KiB caps it at two workgroups per CU, so the dispatcher spreads
     // them (at 32 KiB it packed four on some CUs and none on others: 4,096 x 4 MiB measured
-    // 96.6 instead of 65.4 ms).
+    // 96.6 instead of 65.4 ms).  The wide ring is three stages deep (the producer runs two ahead:
+    // quad_ring.hpp), so a fourth, unused stage is left of that region and the LDS is what it was.
+    constexpr int DEPTH = COMPACT ? kLatRing : kQuadWideRing;
     __shared__ uint4 ring[COMPACT ? 1 : 2][kLatRing][16][G];
     __shared__ uint32_t lds_a[kQuadLeaves][8];
     __shared__ uint32_t lds_b[kQuadLeaves / 2][8];
+    static_assert(DEPTH * sizeof(ring[0][0]) <= sizeof(ring), "the ring's stages must fit its LDS");
+    static_assert(COMPACT || (3 * sizeof(ring) > (160u << 10) && sizeof(ring) <= (64u << 10) &&
+                              2 * (sizeof(ring) + sizeof(lds_a) + sizeof(lds_b)) <= (160u << 10)),
+                  "the wide K1Q must stay at exactly two workgroups per CU (160 KiB of LDS)");
     const uint32_t lane = threadIdx.x & 63;
     const bool producer = __builtin_amdgcn_readfirstlane(threadIdx.x) < 64;
     const uint32_t c = lane >> 3;                             // leaf within the workgroup
@@ -907,34 +1009,53 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
         // lane (c, j) schedules blocks j, j+8, j+16, ... of leaf c
         Blk cur;
         if (j < v.nb) cur = load_block<ALIGNED>(v.p + 64 * j);
-        for (uint64_t it = 0; it < NI; it++) {
-            const uint64_t b = it * kQuadBlocks + j;
-            if (b < v.nb) {
-                uint32_t w[16];
-                block_words(cur, w);
-                if (b + kQuadBlocks < v.nb) cur = load_block<ALIGNED>(v.p + 64 * (b + kQuadBlocks));
-                uint4* kw = &ring[0][it % kLatRing][0][j * ROW + c];
-#pragma unroll
-                for (int q = 0; q < 16; q++) {
-                    uint32_t u[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const int t = 4 * q + k;
-                        uint32_t wt;
-                        if (t < 16) {
-                            wt = w[t];
-                        } else {
-                            wt = ssig1(w[(t - 2) & 15]) + w[(t - 7) & 15] + ssig0(w[(t - 15) & 15]) + w[t & 15];
-                            w[t & 15] = wt;
-                        }
-                        u[k] = 0u - (kSha256K[t] + wt);   // the consumer subtracts it
-                    }
-                    kw[q * G] = make_uint4(u[0], u[1], u[2], u[3]);
-                }
+        if constexpr (!COMPACT) {
+            // two stages ahead, in slots 0, 1, 2, 0, ...: NI + 1 barriers, like the consumer
+            uint4* const kw0 = &ring[0][0][0][j * ROW + c];
+            uint32_t slot = 0;
+            for (uint64_t s = 0; s < quad_ring::stages_before_first_barrier(DEPTH); s++) {
+                if (s < NI) quad_produce_block<ALIGNED, G>(v, cur, s * kQuadBlocks + j, kw0 + slot * 16 * G);
+                slot = quad_ring::next_slot(slot, DEPTH);
             }
-            __syncthreads();   // stage it full  /  stage it-1 free
+            __syncthreads();       // stages 0 and 1 full
+            for (uint64_t it = 0; it < NI; it++) {
+                const uint64_t s = quad_ring::stage_written_after_barrier(it, DEPTH);
+                if (s < NI) quad_produce_block<ALIGNED, G>(v, cur, s * kQuadBlocks + j, kw0 + slot * 16 * G);
+                slot = quad_ring::next_slot(slot, DEPTH);
+                __syncthreads();   // stage it + 2 full  /  stage it free
+            }
+        } else {
+            // one stage ahead.  (The block written out here, not through quad_produce_block: the
+            // compact kernel's generated code follows the shape of its source, and stays as measured.)
+            for (uint64_t it = 0; it < NI; it++) {
+                const uint64_t b = it * kQuadBlocks + j;
+                if (b < v.nb) {
+                    uint32_t w[16];
+                    block_words(cur, w);
+                    if (b + kQuadBlocks < v.nb) cur = load_block<ALIGNED>(v.p + 64 * (b + kQuadBlocks));
+                    uint4* kw = &ring[0][it % kLatRing][0][j * ROW + c];
+#pragma unroll
+                    for (int q = 0; q < 16; q++) {
+                        uint32_t u[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const int t = 4 * q + k;
+                            uint32_t wt;
+                            if (t < 16) {
+                                wt = w[t];
+                            } else {
+                                wt = ssig1(w[(t - 2) & 15]) + w[(t - 7) & 15] + ssig0(w[(t - 15) & 15]) + w[t & 15];
+                                w[t & 15] = wt;
+                            }
+                            u[k] = 0u - (kSha256K[t] + wt);   // the consumer subtracts it
+                        }
+                        kw[q * G] = make_uint4(u[0], u[1], u[2], u[3]);
+                    }
+                }
+                __syncthreads();   // stage it full  /  stage it-1 free
+            }
+            __syncthreads();
         }
-        __syncthreads();
     } else {
         // The consumer carries the serial chains: give it issue priority over a producer or a
         // second consumer on its SIMD.  Measured on MI355X (tools/ab_builds.sh,
@@ -968,6 +1089,7 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; k++) xf[k] = x[k];
         const uint64_t NS = uniform_u64(NI);
+        uint32_t wslot = 0;   // wide: the ring slot of stage it (3 is no power of two: walked along)
         for (uint64_t it = 0; it < NS;) {
             // A run of whole stages, its own loop, so the register path compiles (and is counted by
             // deoss_amd/isa.py) without the per-block path inside it.  Its length is known before it
@@ -975,11 +1097,22 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
             // boundary or inside stage nb / 8.  So every leaf still running runs all of the run and
             // xf is set once at its end: a scalar trip count, no vote and no copies per stage on the
             // chain's wave.  A wave of mixed lengths takes one run per distinct leaf end.
-            const bool running = vq.active && vq.nb > it * kQuadBlocks;
-            const uint64_t end = uniform_u64(wave_min_u64(running ? vq.nb / kQuadBlocks : NS));
-            for (; it < end; it++) {
-                quad_stage_regs<G, ROW, COMPACT>(x, col + (it % kLatRing) * 16 * G + p * G, sh, msk);
-                __syncthreads();
+            // (The wide kernel takes the run's arithmetic from quad_ring.hpp, which the host test
+            // steps; the compact kernel keeps the same expressions written out, because its
+            // generated code follows the shape of its source and stays as measured.)
+            const bool running = COMPACT ? vq.active && vq.nb > it * kQuadBlocks
+                                         : quad_ring::leaf_running(vq.active, vq.nb, it);
+            const uint64_t end = uniform_u64(wave_min_u64(COMPACT ? (running ? vq.nb / kQuadBlocks : NS)
+                                                                  : quad_ring::leaf_run_end(running, vq.nb, NS)));
+            if constexpr (COMPACT) {
+                for (; it < end; it++) {
+                    quad_stage_regs<G, ROW, COMPACT>(x, col + (it % kLatRing) * 16 * G + p * G, sh, msk);
+                    __syncthreads();
+                }
+            } else if (it < end) {
+                // the whole run is one stream; its last stage drains and reads nothing beyond itself
+                wslot = quad_run_xstage<G, ROW>(x, col + p * G, wslot, end - it, sh, msk);
+                it = end;
             }
             if (running) {
 #pragma unroll
@@ -987,8 +1120,10 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
             }
             if (it == NS) break;
             // a leaf of the wave ends strictly inside stage it: the per-block path; else the next run
-            if (!__any(vq.active && vq.nb > it * kQuadBlocks && vq.nb < (it + 1) * kQuadBlocks)) continue;
-            const uint4* kw = col + (it % kLatRing) * 16 * G;
+            if (!__any(COMPACT ? vq.active && vq.nb > it * kQuadBlocks && vq.nb < (it + 1) * kQuadBlocks
+                               : quad_ring::leaf_ends_inside(vq.active, vq.nb, it)))
+                continue;
+            const uint4* kw = col + (COMPACT ? (uint32_t)(it % kLatRing) : wslot) * 16 * G;
             const uint64_t b0 = it * kQuadBlocks;
             for (uint32_t k = 0; k < kQuadBlocks; k++) {
                 const uint4* kb = kw + k * ROW;
@@ -1001,6 +1136,7 @@ __global__ __launch_bounds__(kLatThreads) void leaf_kernel_quad(LeafArgs a) {
             }
             __syncthreads();
             it++;
+            wslot = quad_ring::next_slot(wslot, DEPTH);
         }
         // full state on the e-quad's first lane: (a,b,c,d) from the a-quad 8 lanes up
         uint32_t st[8];

@@ -123,11 +123,14 @@ def analyse(asm: str, sym: str = K1_SYMBOL) -> dict:
 
 def analyse_split(asm: str, sym: str) -> dict:
     loops = list(_loops(_function_body(asm, sym)))
-    # K1Q runs whole ring stages (8 blocks from registers as one step stream: 8 x 64 steps plus
-    # the two that drain it, each ending in one v_add3_u32; 4 ds_read_b128 per block since the
-    # words are spread over a quad's lanes) when no leaf of the wave ends inside them: that loop
-    # is the bench path; otherwise the per-block loop (16 reads)
-    stage = _smallest(loops, lambda l: sum(x.startswith("v_add3_u32") for x in l) >= 8 * 64 + 2
+    # K1Q runs whole ring stages (8 blocks from registers, 4 ds_read_b128 per block since the words
+    # are spread over a quad's lanes) when no leaf of the wave ends inside them: that loop is the
+    # bench path; otherwise the per-block loop (16 reads).  The wide kernel's run of stages is one
+    # step stream, so its steady-state loop holds exactly 8 x 64 steps (one v_add3_u32 each) and
+    # the fill and drain are peeled blocks outside it, in no loop of their own: the smallest
+    # loop with 8 x 64 steps and 32 reads is the steady state, any loop around it is larger.
+    # (A stream per stage, as in the compact kernel, has 8 x 64 + 2: the two steps that drain it.)
+    stage = _smallest(loops, lambda l: sum(x.startswith("v_add3_u32") for x in l) >= 8 * 64
                       and sum(x.startswith("ds_read_b128") for x in l) >= 32)
     if stage is not None:
         prod = _smallest(loops, lambda l: sum(x.startswith("ds_write_b128") for x in l) >= 16)

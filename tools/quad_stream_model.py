@@ -4,8 +4,11 @@
 Expands the DM_QS_* macros of the kernel header with the C preprocessor, interprets the
 resulting instruction text on the 16 lanes of one DPP row (two leaves: e-quads on lanes 0..7,
 a-quads 8 lanes up) and compares the chaining state after 1, 2, 3, 8, 9 and 2 x 8 linked blocks
-with hashlib.sha256.  It also checks the DPP wait-state rule: no DPP source VGPR is written by
-either of the two preceding instructions.  No GPU needed:  python tools/quad_stream_model.py
+with hashlib.sha256: a stream per ring stage (the compact kernel), and the stages of a run as ONE
+stream with a link at every stage boundary, as the wide kernel sequences it ([8, 8],
+[8, 8, 8, 8], [8, 8, 3]).  It also checks the DPP wait-state rule: no DPP source VGPR is written
+by either of the two preceding instructions (the barrier between stages counts as none).
+No GPU needed:  python tools/quad_stream_model.py
 """
 import hashlib
 import os
@@ -136,8 +139,14 @@ def load_k(row, prefix, kws):
             row.v[name] = [kws[(i >> 2) & 1][16 * t + 4 * (i & 3) + w] for i in range(16)]
 
 
-def run_leaves(msgs, stages, code):
-    """msgs: two byte strings of equal whole-block length; stages: blocks per stage, in order."""
+def run_leaves(msgs, stages, code, one_stream=False):
+    """msgs: two byte strings of equal whole-block length; stages: blocks per stage, in order.
+    one_stream: the wide kernel's run of stages (quad_run_xstage): P = x and the fill at the first
+    block of the first stage only, a DM_QS_LINKQ at every stage boundary (the next stage's block 0
+    gives n0..n2), the drain at the last block of the last stage.  The barrier between two stages
+    is no instruction: the DPP wait-state rule is checked straight across it."""
+    if one_stream:
+        stages = [sum(stages)]
     row = Row()
     # x: e-quads (e,f,g,h), a-quads (c,d,a,b); leaf l's e-quad = lanes 4l.., a-quad 8 up
     for k in range(4):
@@ -182,6 +191,17 @@ def main():
         good = got == want
         ok &= good
         print("stages %-8s %5d instructions  %s" % (stages, cnt, "ok" if good else "MISMATCH"))
+    # the wide kernel: the stages of a run as one stream, linked at every stage boundary
+    for stages in ([8, 8], [8, 8, 8, 8], [8, 8, 3]):
+        nb = sum(stages)
+        msgs = [bytes((11 * i + 5 * l + nb) & 255 for i in range(64 * nb - 9)) for l in range(2)]
+        padded = [m + b"\x80" + struct.pack(">Q", 8 * len(m)) for m in msgs]
+        got, cnt = run_leaves(padded, stages, code, one_stream=True)
+        _, per_stage = run_leaves(padded, stages, code)
+        good = got == [hashlib.sha256(m).digest() for m in msgs]
+        ok &= good
+        print("run    %-14s %5d instructions (%d with a stream per stage)  %s" %
+              (stages, cnt, per_stage, "ok" if good else "MISMATCH"))
     return 0 if ok else 1
 
 
