@@ -1,0 +1,206 @@
+// aes_kernels.hpp -- gfx950 AES-CBC for the cipher branch of FullProcessing / Retrievefile
+// (cipher_scheme.hpp says how the SDK uses it).  Included by merkle_capi.hip only (cipher_capi.inl).
+//
+// Both kernels are T-table AES (FIPS-197 §5; the decrypt side is the equivalent inverse cipher of
+// §5.3.5): SubBytes + ShiftRows + MixColumns of one state byte is one 32-bit table lookup, a round
+// is 16 lookups and 16 xors.  The tables are generated at compile time (aes_host.hpp), copied to
+// LDS at kernel start (4 x 1 KiB rotations of one table + the S-box for the last round); the round
+// keys are expanded on the host and arrive as kernel arguments.
+//
+//   aes_cbc_decrypt_kernel  P_i = D(C_i) ^ C_{i-1} is parallel over blocks: one lane per 16-byte
+//       block, x over a segment's blocks and y over segments (launch_rs's grid), 16-byte loads,
+//       non-temporal 16-byte stores, out of place and compacting (the padding block is checked,
+//       not written).
+//   aes_cbc_encrypt_kernel  C_i = E(P_i ^ C_{i-1}) is one serial chain per segment.  FOUR lanes (a
+//       DPP quad) carry a chain, lane j the state column j: it looks its own four bytes up in the
+//       four tables, and ShiftRows is three quad_perm reads of the neighbours' lookups (xor-ed on
+//       the way), so a round is 4 address extracts, 4 independent ds_read_b32, 4 xors.  The state
+//       never leaves registers; the plaintext is loaded kAesDepth blocks ahead.  16 chains per
+//       wave, one wave per workgroup: 256 segments spread over 16 CUs' SIMDs.
+//       Latency-bound like the SHA-256 chains: a throughput path.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "aes_host.hpp"
+
+namespace dm {
+
+constexpr int kAesDecThreads = 256;
+constexpr int kAesEncThreads = 64;    // one wave: 16 chains x 4 lanes
+constexpr int kAesLanesPerChain = 4;
+constexpr int kAesDepth = 8;          // plaintext blocks in flight ahead of the chain
+constexpr uint32_t kAesPadWord = 0x10101010u;   // PKCS#7 padding of a whole block
+
+struct AesKey {
+    uint32_t w[dm_aes::kMaxKeyWords];   // 240 bytes, little-endian column words, round-major
+};
+
+struct AesEncArgs {
+    AesKey rk;
+    uint32_t iv[4];
+    uint8_t* dev;        // segment s: nblk plaintext blocks at dev + s * stride, overwritten by nblk + 1 ciphertext blocks
+    uint64_t stride;
+    uint64_t nblk;
+    uint64_t nseg;
+};
+
+struct AesDecArgs {
+    AesKey rk;           // equivalent-inverse-cipher keys
+    uint32_t iv[4];
+    const uint8_t* in;   // segment s: nblk ciphertext blocks at in + s * in_stride
+    uint64_t in_stride;
+    uint64_t nblk;       // >= 2: the last one is the padding block
+    uint64_t nseg;
+    uint8_t* out;        // segment s: nblk - 1 plaintext blocks at out + s * out_stride
+    uint64_t out_stride;
+    uint8_t* pad_ok;     // [nseg]: 1 iff the last block decrypts to sixteen 0x10 bytes
+};
+
+__device__ __constant__ static const dm_aes::Tables kAesTables{};
+
+__device__ __forceinline__ uint32_t aes_rotl(uint32_t x, uint32_t n) { return (x << n) | (x >> (32 - n)); }
+
+// tab[r * 256 + a] = rotl(t0[a], 8 r) for r < 4; tab[1024 + a] = the S-box byte in all four bytes.
+template <int THREADS>
+__device__ __forceinline__ void aes_fill_lds(uint32_t* tab, const uint32_t* t0, const uint8_t* sb) {
+    for (uint32_t t = threadIdx.x; t < 256; t += THREADS) {
+        const uint32_t e = t0[t];
+        tab[t] = e;
+        tab[256 + t] = aes_rotl(e, 8);
+        tab[512 + t] = aes_rotl(e, 16);
+        tab[768 + t] = aes_rotl(e, 24);
+        tab[1024 + t] = (uint32_t)sb[t] * 0x01010101u;
+    }
+    __syncthreads();
+}
+
+// Lane i of a quad reads lane (i + R) & 3's value.
+template <int R>
+__device__ __forceinline__ uint32_t aes_quad_rot(uint32_t v) {
+    constexpr int ctrl = ((0 + R) & 3) | (((1 + R) & 3) << 2) | (((2 + R) & 3) << 4) | (((3 + R) & 3) << 6);
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xf, 0xf, true);
+}
+
+// One block on a quad: x = this lane's column of (plaintext ^ chain), rk = its column of every
+// round key.  Row r of the output column i comes from input column i + r (ShiftRows).
+template <int NR>
+__device__ __forceinline__ uint32_t aes_encrypt_quad(uint32_t x, const uint32_t (&rk)[NR + 1], const uint32_t* tab) {
+    x ^= rk[0];
+#pragma unroll
+    for (int r = 1; r < NR; r++) {
+        const uint32_t t0 = tab[x & 0xffu];
+        const uint32_t t1 = tab[256 + ((x >> 8) & 0xffu)];
+        const uint32_t t2 = tab[512 + ((x >> 16) & 0xffu)];
+        const uint32_t t3 = tab[768 + (x >> 24)];
+        x = t0 ^ aes_quad_rot<1>(t1) ^ aes_quad_rot<2>(t2) ^ aes_quad_rot<3>(t3) ^ rk[r];
+    }
+    const uint32_t u0 = tab[1024 + (x & 0xffu)] & 0x000000ffu;
+    const uint32_t u1 = tab[1024 + ((x >> 8) & 0xffu)] & 0x0000ff00u;
+    const uint32_t u2 = tab[1024 + ((x >> 16) & 0xffu)] & 0x00ff0000u;
+    const uint32_t u3 = tab[1024 + (x >> 24)] & 0xff000000u;
+    return u0 ^ aes_quad_rot<1>(u1) ^ aes_quad_rot<2>(u2) ^ aes_quad_rot<3>(u3) ^ rk[NR];
+}
+
+// Grid: ceil(nseg / 16) workgroups of one wave.  Every segment has the same block count, so the
+// loop bounds are uniform over the wave; a quad is wholly inside or outside nseg.
+template <int NR>
+__global__ __launch_bounds__(kAesEncThreads)
+void aes_cbc_encrypt_kernel(AesEncArgs a) {
+    __shared__ uint32_t tab[5 * 256];
+    aes_fill_lds<kAesEncThreads>(tab, kAesTables.te0, kAesTables.sbox);
+    const uint32_t j = threadIdx.x & 3u;
+    const uint64_t chain = ((uint64_t)blockIdx.x * kAesEncThreads + threadIdx.x) / kAesLanesPerChain;
+    if (chain >= a.nseg) return;
+    uint32_t rk[NR + 1];
+#pragma unroll
+    for (int r = 0; r <= NR; r++) {
+        const uint32_t k01 = j & 1u ? a.rk.w[4 * r + 1] : a.rk.w[4 * r];
+        const uint32_t k23 = j & 1u ? a.rk.w[4 * r + 3] : a.rk.w[4 * r + 2];
+        rk[r] = j & 2u ? k23 : k01;
+    }
+    const uint32_t iv01 = j & 1u ? a.iv[1] : a.iv[0], iv23 = j & 1u ? a.iv[3] : a.iv[2];
+    uint32_t c = j & 2u ? iv23 : iv01;
+    uint32_t* p = reinterpret_cast<uint32_t*>(a.dev + chain * a.stride) + j;   // this lane's column of block 0
+    const uint64_t nblk = a.nblk, total = nblk + 1;   // the padding block comes after the data
+    uint32_t pf[kAesDepth];
+#pragma unroll
+    for (int i = 0; i < kAesDepth; i++) pf[i] = (uint64_t)i < nblk ? p[4 * i] : kAesPadWord;
+    for (uint64_t b0 = 0; b0 < total; b0 += kAesDepth) {
+#pragma unroll
+        for (int i = 0; i < kAesDepth; i++) {
+            const uint64_t b = b0 + i;
+            if (b >= total) break;
+            const uint32_t x = pf[i] ^ c;
+            // block b + kAesDepth (still plaintext: the chain has written blocks < b only)
+            pf[i] = b + kAesDepth < nblk ? p[4 * (b + kAesDepth)] : kAesPadWord;
+            c = aes_encrypt_quad<NR>(x, rk, tab);
+            p[4 * b] = c;
+        }
+    }
+}
+
+__device__ __forceinline__ uint4 aes_load16(const uint8_t* p) { return *reinterpret_cast<const uint4*>(p); }
+
+// The equivalent inverse cipher on a whole block in one lane.  Row r of output column i comes from
+// input column i - r (InvShiftRows).
+template <int NR>
+__device__ __forceinline__ uint4 aes_decrypt_block(uint4 cblk, const AesKey& dk, const uint32_t* tab) {
+    uint32_t s[4] = {cblk.x ^ dk.w[0], cblk.y ^ dk.w[1], cblk.z ^ dk.w[2], cblk.w ^ dk.w[3]};
+#pragma unroll
+    for (int r = 1; r < NR; r++) {
+        uint32_t t[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            t[i] = tab[s[i] & 0xffu] ^ tab[256 + ((s[(i + 3) & 3] >> 8) & 0xffu)] ^
+                   tab[512 + ((s[(i + 2) & 3] >> 16) & 0xffu)] ^ tab[768 + (s[(i + 1) & 3] >> 24)] ^ dk.w[4 * r + i];
+#pragma unroll
+        for (int i = 0; i < 4; i++) s[i] = t[i];
+    }
+    uint32_t o[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        o[i] = (tab[1024 + (s[i] & 0xffu)] & 0x000000ffu) ^ (tab[1024 + ((s[(i + 3) & 3] >> 8) & 0xffu)] & 0x0000ff00u) ^
+               (tab[1024 + ((s[(i + 2) & 3] >> 16) & 0xffu)] & 0x00ff0000u) ^
+               (tab[1024 + (s[(i + 1) & 3] >> 24)] & 0xff000000u) ^ dk.w[4 * NR + i];
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// Grid: x strides over a segment's blocks, y over segments (rs_grid).
+template <int NR>
+__global__ __launch_bounds__(kAesDecThreads)
+void aes_cbc_decrypt_kernel(AesDecArgs a) {
+    __shared__ uint32_t tab[5 * 256];
+    aes_fill_lds<kAesDecThreads>(tab, kAesTables.td0, kAesTables.inv);
+    const uint64_t ustride = (uint64_t)gridDim.x * kAesDecThreads;
+    const uint4 iv = make_uint4(a.iv[0], a.iv[1], a.iv[2], a.iv[3]);
+    for (uint64_t seg = blockIdx.y; seg < a.nseg; seg += gridDim.y) {
+        const uint8_t* in = a.in + seg * a.in_stride;
+        uint8_t* out = a.out + seg * a.out_stride;
+        uint64_t u = (uint64_t)blockIdx.x * kAesDecThreads + threadIdx.x;
+        // register double buffer: the next block's loads are in flight while this one is decrypted
+        uint4 nc = iv, np = iv;
+        if (u < a.nblk) {
+            nc = aes_load16(in + u * 16);
+            if (u) np = aes_load16(in + (u - 1) * 16);
+        }
+        for (; u < a.nblk; u += ustride) {
+            const uint4 cblk = nc, prev = np;
+            if (u + ustride < a.nblk) {
+                nc = aes_load16(in + (u + ustride) * 16);
+                np = aes_load16(in + (u + ustride - 1) * 16);
+            }
+            uint4 x = aes_decrypt_block<NR>(cblk, a.rk, tab);
+            x.x ^= prev.x;
+            x.y ^= prev.y;
+            x.z ^= prev.z;
+            x.w ^= prev.w;
+            if (u + 1 < a.nblk)
+                rs_store(out + u * 16, x);
+            else
+                a.pad_ok[seg] = (x.x == kAesPadWord && x.y == kAesPadWord && x.z == kAesPadWord && x.w == kAesPadWord) ? 1 : 0;
+        }
+    }
+}
+
+}  // namespace dm

@@ -1,0 +1,132 @@
+// cipher_capi.inl -- AES-CBC on the GPU (dm_aes_cbc_*_device_async; include/deoss_merkle.h) and the
+// launch helpers dm_process_cipher_buffer / dm_restore_cipher_buffer use.  Part of merkle_capi.hip
+// (after rs_capi.inl: the decrypt kernel shares rs_grid and rs_store).
+//
+// The cipher branch of cess-go-sdk process.FullProcessing / Retrievefile (cipher != ""): the scheme
+// is recalled, not pinned (cipher_scheme.hpp); the AES-CBC core is FIPS-197 /
+// SP 800-38A.  The key schedule runs on the host per call; the round keys are kernel arguments and
+// never sit in a device buffer.
+#include "aes_kernels.hpp"
+#include "cipher_scheme.hpp"
+
+namespace {
+
+// A cipher string as the kernels take it: both key schedules and the IV.
+struct CipherKey {
+    dm_aes::KeySchedule ks;
+    uint32_t iv[4];
+};
+
+void cipher_set_iv(CipherKey& k, const uint8_t iv[16]) { std::memcpy(k.iv, iv, 16); }
+
+// The scheme's key: the cipher's bytes, IV = its first 16.
+int cipher_key(dm_ctx* c, const void* cipher, uint64_t cipher_len, CipherKey& k) {
+    if (!cipher || !dm_aes::expand_key(static_cast<const uint8_t*>(cipher), cipher_len, k.ks))
+        return fail(c, DM_ERR_INVALID, "%s", dm_cipher::kKeyLenError);
+    uint8_t iv[16];
+    dm_cipher::iv_of(static_cast<const uint8_t*>(cipher), iv);
+    cipher_set_iv(k, iv);
+    return DM_OK;
+}
+
+template <class F>
+void aes_for_rounds(int nr, F&& f) {
+    switch (nr) {
+        case 10: f(std::integral_constant<int, 10>()); break;
+        case 12: f(std::integral_constant<int, 12>()); break;
+        default: f(std::integral_constant<int, 14>()); break;
+    }
+}
+
+// nseg chains in place: `plain` bytes at dev + t * stride become plain + 16 bytes of ciphertext.
+hipError_t launch_aes_encrypt(hipStream_t s, const CipherKey& k, uint8_t* dev, uint64_t stride, uint64_t plain,
+                              uint64_t nseg) {
+    dm::AesEncArgs a{};
+    std::memcpy(a.rk.w, k.ks.enc, sizeof a.rk.w);
+    std::memcpy(a.iv, k.iv, 16);
+    a.dev = dev;
+    a.stride = stride;
+    a.nblk = plain / 16;
+    a.nseg = nseg;
+    const dim3 grid((uint32_t)ceil_div(nseg * dm::kAesLanesPerChain, dm::kAesEncThreads)), block(dm::kAesEncThreads);
+    aes_for_rounds(k.ks.rounds, [&](auto NR) {
+        hipLaunchKernelGGL(dm::aes_cbc_encrypt_kernel<decltype(NR)::value>, grid, block, 0, s, a);
+    });
+    return hipGetLastError();
+}
+
+// nseg x cipher_bytes of ciphertext -> nseg x (cipher_bytes - 16) of plaintext at out + t * out_stride,
+// pad_ok[t] = the padding block was sixteen 0x10 bytes.
+hipError_t launch_aes_decrypt(Dev& d, hipStream_t s, const CipherKey& k, const uint8_t* in, uint64_t in_stride,
+                              uint64_t cipher_bytes, uint64_t nseg, uint8_t* out, uint64_t out_stride, uint8_t* pad_ok) {
+    dm::AesDecArgs a{};
+    std::memcpy(a.rk.w, k.ks.dec, sizeof a.rk.w);
+    std::memcpy(a.iv, k.iv, 16);
+    a.in = in;
+    a.in_stride = in_stride;
+    a.nblk = cipher_bytes / 16;
+    a.nseg = nseg;
+    a.out = out;
+    a.out_stride = out_stride;
+    a.pad_ok = pad_ok;
+    const dim3 grid = rs_grid(d, a.nblk, nseg), block(dm::kAesDecThreads);
+    static_assert(dm::kAesDecThreads == dm::kRsThreads, "rs_grid sizes x for kRsThreads lanes");
+    aes_for_rounds(k.ks.rounds, [&](auto NR) {
+        hipLaunchKernelGGL(dm::aes_cbc_decrypt_kernel<decltype(NR)::value>, grid, block, 0, s, a);
+    });
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int dm_aes_cbc_encrypt_device_async(dm_ctx* ctx, const void* key, uint64_t key_len, const uint8_t iv[16], void* dev,
+                                    uint64_t stride, uint64_t plain, uint64_t nseg, void* stream) {
+    if (!ctx || !key || !iv) return bad_arg();
+    const int g = device_of(ctx, dev);
+    CallLock lk(ctx, g, kReserved);
+    dm_ctx* c = ctx;
+    CipherKey k;
+    if (!dm_aes::expand_key(static_cast<const uint8_t*>(key), key_len, k.ks))
+        return fail(c, DM_ERR_INVALID, "%s", dm_cipher::kKeyLenError);
+    cipher_set_iv(k, iv);
+    if (nseg == 0) return DM_OK;
+    if (!dev || !is_aligned16(dev) || plain % 16 || stride % 16 || plain + 16 > stride)
+        return fail(c, DM_ERR_INVALID,
+                    "dm_aes_cbc_encrypt_device_async: need a 16-byte aligned buffer and stride, plain %% 16 == 0 and "
+                    "plain + 16 <= stride");
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    HIP_TRY(launch_aes_encrypt(s, k, static_cast<uint8_t*>(dev), stride, plain, nseg));
+    return DM_OK;
+}
+
+int dm_aes_cbc_decrypt_device_async(dm_ctx* ctx, const void* key, uint64_t key_len, const uint8_t iv[16],
+                                    const void* dev_in, uint64_t in_stride, uint64_t cipher_bytes, uint64_t nseg,
+                                    void* dev_out, uint64_t out_stride, void* dev_pad_ok, void* stream) {
+    if (!ctx || !key || !iv) return bad_arg();
+    const int g = device_of(ctx, dev_in);
+    CallLock lk(ctx, g, kReserved);
+    dm_ctx* c = ctx;
+    CipherKey k;
+    if (!dm_aes::expand_key(static_cast<const uint8_t*>(key), key_len, k.ks))
+        return fail(c, DM_ERR_INVALID, "%s", dm_cipher::kKeyLenError);
+    cipher_set_iv(k, iv);
+    if (nseg == 0) return DM_OK;
+    if (!dev_in || !dev_out || !dev_pad_ok || !is_aligned16(dev_in) || !is_aligned16(dev_out) || cipher_bytes % 16 ||
+        cipher_bytes < 32 || in_stride % 16 || out_stride % 16 || in_stride < cipher_bytes ||
+        out_stride < cipher_bytes - 16)
+        return fail(c, DM_ERR_INVALID,
+                    "dm_aes_cbc_decrypt_device_async: need 16-byte aligned buffers and strides, cipher_bytes %% 16 == 0, "
+                    "cipher_bytes >= 32 and strides that hold a segment");
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    HIP_TRY(launch_aes_decrypt(d, s, k, static_cast<const uint8_t*>(dev_in), in_stride, cipher_bytes, nseg,
+                               static_cast<uint8_t*>(dev_out), out_stride, static_cast<uint8_t*>(dev_pad_ok)));
+    return DM_OK;
+}
+
+}  // extern "C"

@@ -2089,6 +2089,7 @@ int dm_root_batch(dm_ctx* ctx, const void* const* objs, const uint64_t* lens, ui
 #include "merkle_stream.inl"
 #include "files_capi.inl"
 #include "rs_capi.inl"
+#include "cipher_capi.inl"
 #include "process_capi.inl"
 #include "fullproc_capi.inl"
 #include "restore_capi.inl"

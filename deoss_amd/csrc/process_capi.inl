@@ -71,6 +71,9 @@ int process_dev(dm_rs* r, Dev& d, hipStream_t s, uint8_t* obj, uint64_t len, uin
     return DM_OK;
 }
 
+int process_staged(dm_rs* r, Dev& d, const std::vector<uint64_t>& first, uint64_t segment, void* const* frags_out,
+                   uint8_t* const* seg_hashes, uint8_t* const* frag_hashes, uint8_t* fids);
+
 // Host objects -> device (segment-aligned, zero-padded) -> process_segments -> host outputs.
 // Per-object outputs are nullable (frags_out / seg_hashes / frag_hashes may be NULL arrays or hold
 // NULL entries); fids (nobj x 32) is required.  Runs on d.stream, synchronous.
@@ -79,8 +82,6 @@ int process_host(dm_rs* r, Dev& d, const void* const* objs, const uint64_t* lens
     dm_ctx* c = r->c;
     hipStream_t s = d.stream;
     RC_TRY(begin_call(c, d, s));
-    const int k = r->k, m = r->m, total = k + m;
-    const uint64_t frag = segment / (uint64_t)k;
     std::vector<uint64_t> first(nobj + 1, 0), off(nobj);
     for (uint64_t o = 0; o < nobj; o++) {
         first[o + 1] = first[o] + ceil_div(lens[o], segment);
@@ -93,6 +94,18 @@ int process_host(dm_rs* r, Dev& d, const void* const* objs, const uint64_t* lens
         const uint64_t pad = (first[o + 1] - first[o]) * segment - lens[o];
         if (pad) HIP_TRY(hipMemsetAsync(d.data.u8() + off[o] + lens[o], 0, pad, s));
     }
+    return process_staged(r, d, first, segment, frags_out, seg_hashes, frag_hashes, fids);
+}
+
+// The part of process_host after staging: first.back() whole segments lie at d.data (padding zeroed
+// or, with a cipher, already ciphertext), queued on d.stream.
+int process_staged(dm_rs* r, Dev& d, const std::vector<uint64_t>& first, uint64_t segment, void* const* frags_out,
+                   uint8_t* const* seg_hashes, uint8_t* const* frag_hashes, uint8_t* fids) {
+    dm_ctx* c = r->c;
+    hipStream_t s = d.stream;
+    const int k = r->k, m = r->m, total = k + m;
+    const uint64_t frag = segment / (uint64_t)k;
+    const uint64_t nobj = first.size() - 1, S = first[nobj];
     DevBuf& work = rs_ln(r, d).work;
     HIP_TRY(work.ensure(S * (uint64_t)m * frag + nobj * 32));
     uint8_t* parity = work.u8();
@@ -118,6 +131,29 @@ int process_host(dm_rs* r, Dev& d, const void* const* objs, const uint64_t* lens
     }
     HIP_TRY(hipStreamSynchronize(s));
     return DM_OK;
+}
+
+// process_host for one object with a cipher (cipher_scheme.hpp): the object's P = segment - 16 byte
+// pieces go to the device at stride `segment` (one 2-D copy with source pitch P), the last piece's
+// tail is zeroed, the encrypt kernel turns every piece into one segment of ciphertext in place, and
+// from there process_staged runs as for a plain object of nseg whole segments.
+int process_cipher_host(dm_rs* r, Dev& d, const CipherKey& key, const uint8_t* host, uint64_t len, uint64_t segment,
+                        void* frags_out, uint8_t* seg_hashes, uint8_t* frag_hashes, uint8_t* fid) {
+    dm_ctx* c = r->c;
+    hipStream_t s = d.stream;
+    RC_TRY(begin_call(c, d, s));
+    const dm_cipher::Geometry g = dm_cipher::geometry(len, segment);
+    HIP_TRY(d.data.ensure(g.nseg * segment + kAlign));
+    const uint64_t full = len / g.piece, rem = len - full * g.piece;
+    if (full)
+        HIP_TRY(hipMemcpy2DAsync(d.data.p, segment, host, g.piece, g.piece, full, hipMemcpyHostToDevice, s));
+    if (rem) {
+        uint8_t* last = d.data.u8() + full * segment;
+        HIP_TRY(hipMemcpyAsync(last, host + full * g.piece, rem, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(last + rem, 0, g.piece - rem, s));
+    }
+    HIP_TRY(launch_aes_encrypt(s, key, d.data.u8(), segment, g.piece, g.nseg));
+    return process_staged(r, d, {0, g.nseg}, segment, &frags_out, &seg_hashes, &frag_hashes, fid);
 }
 
 int process_check(dm_rs* r, uint64_t len, uint64_t segment) {
@@ -157,6 +193,27 @@ int dm_process_buffer(dm_rs* r, const void* host, uint64_t len, uint64_t segment
     if (!fid || (!host && len)) return fail(c, DM_ERR_INVALID, "dm_process_buffer: null argument");
     RC_TRY(process_check(r, len, segment));
     return process_host(r, c->devs[g], &host, &len, 1, segment, &frags_out, &seg_hashes, &frag_hashes, fid);
+}
+
+int dm_process_cipher_buffer(dm_rs* r, const void* host, uint64_t len, uint64_t segment, const void* cipher,
+                             uint64_t cipher_len, void* frags_out, uint8_t* seg_hashes, uint8_t* frag_hashes,
+                             uint8_t fid[32]) {
+    if (!r) return bad_arg();
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    if (!fid || (!host && len)) return fail(c, DM_ERR_INVALID, "dm_process_cipher_buffer: null argument");
+    RC_TRY(process_check(r, len, segment));
+    if (!dm_cipher::segment_ok(segment))
+        return fail(c, DM_ERR_INVALID, "segment size %llu has no room for a block and its padding block",
+                    (unsigned long long)segment);
+    CipherKey key;
+    RC_TRY(cipher_key(c, cipher, cipher_len, key));
+    Dev& d = c->devs[g];
+    const int rc = process_cipher_host(r, d, key, static_cast<const uint8_t*>(host), len, segment, frags_out,
+                                       seg_hashes, frag_hashes, fid);
+    if (rc != DM_OK) (void)hipStreamSynchronize(d.stream);   // no copy from the caller's memory stays queued
+    return rc;
 }
 
 int dm_process_batch(dm_rs* r, const void* const* objs, const uint64_t* lens, uint64_t nobj, uint64_t segment,

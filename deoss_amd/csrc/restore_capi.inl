@@ -143,7 +143,7 @@ int rt_hash(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<uint64_t>& addrs
 }
 
 enum : uint8_t { kFragAbsent = 0, kFragUsed = 1, kFragSpare = 2, kFragBad = 3 };
-enum : uint8_t { kSegOk = 0, kSegTooFew = 1, kSegMismatch = 2 };
+enum : uint8_t { kSegOk = 0, kSegTooFew = 1, kSegMismatch = 2, kSegBadPadding = 3 };
 
 // Fragment states of ns segments -> statuses: the first k good fragments of a segment are used, the
 // other good ones spare; a segment with fewer than k good ones is kSegTooFew (its good fragments
@@ -176,9 +176,13 @@ int restore_check(dm_rs* r, uint64_t nseg, uint64_t size, uint64_t segment) {
     return DM_OK;
 }
 
+// key (nullable): the object was uploaded with a cipher (cipher_scheme.hpp).  Every name and the
+// fid are of ciphertext, so steps 1-4 run as without one; then the segments are decrypted into
+// scratch, and `size` counts plaintext bytes.  A padding block that is not sixteen 0x10 bytes (what
+// a wrong cipher looks like) is kSegBadPadding and *ok stays 0: a result, not an error.
 int restore_buffer(dm_rs* r, Dev& d, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
                    const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, void* out,
-                   uint8_t* fst, uint8_t* sst, int* ok) {
+                   uint8_t* fst, uint8_t* sst, int* ok, const CipherKey* key = nullptr) {
     dm_ctx* c = r->c;
     hipStream_t s = d.stream;
     RC_TRY(begin_call(c, d, s));
@@ -190,7 +194,9 @@ int restore_buffer(dm_rs* r, Dev& d, const void* const* frags, const uint8_t* fr
         for (int j = k; j < total; j++) npar += frags[t * total + j] != nullptr;
     HIP_TRY(d.data.ensure(nseg * segment + kAlign));
     DevBuf& work = rs_ln(r, d).work;
-    HIP_TRY(work.ensure(npar * frag + 16));
+    // with a cipher: the plaintext pieces and the padding verdicts follow the parity fragments
+    const uint64_t piece = segment - dm_cipher::kBlock, plain_off = round_up(npar * frag + 16, kAlign);
+    HIP_TRY(work.ensure(key ? plain_off + nseg * piece + nseg : npar * frag + 16));
     std::vector<const uint8_t*> dev(NF, nullptr);
     std::vector<uint8_t> good(NF, 0);
     std::vector<uint64_t> addrs, which;
@@ -246,8 +252,24 @@ int restore_buffer(dm_rs* r, Dev& d, const void* const* frags, const uint8_t* fr
         }
     }
     if (!all) return DM_OK;
+    const void* obj = d.data.p;
+    if (key) {   // 4b. ciphertext -> the joined plaintext pieces, every padding block checked
+        uint8_t* plain = work.u8() + plain_off;
+        uint8_t* pad_ok = plain + nseg * piece;
+        HIP_TRY(launch_aes_decrypt(d, s, *key, d.data.u8(), segment, segment, nseg, plain, piece, pad_ok));
+        std::vector<uint8_t> pad(nseg);
+        HIP_TRY(hipMemcpyAsync(pad.data(), pad_ok, nseg, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint64_t t = 0; t < nseg; t++)
+            if (pad[t] != 1) {
+                sst[t] = kSegBadPadding;
+                all = false;
+            }
+        if (!all) return DM_OK;
+        obj = plain;
+    }
     // 5. everything held: the object's bytes, without the padding
-    HIP_TRY(hipMemcpyAsync(out, d.data.p, size, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out, obj, size, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     *ok = 1;
     return DM_OK;
@@ -510,6 +532,37 @@ int dm_restore_buffer(dm_rs* r, const void* const* frags, const uint8_t* frag_na
     std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
     const int rc = restore_buffer(r, c->devs[g], frags, frag_names, seg_names, fid, nseg, size, segment, flags, out,
                                   fst.data(), sst.data(), ok);
+    // no copy from the caller's memory stays queued, whichever way the call ends
+    if (rc != DM_OK || !*ok) (void)hipStreamSynchronize(c->devs[g].stream);
+    if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
+    if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
+    return rc;
+}
+
+int dm_restore_cipher_buffer(dm_rs* r, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
+                             const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
+                             const void* cipher, uint64_t cipher_len, void* out, uint8_t* frag_status,
+                             uint8_t* seg_status, int* ok) {
+    if (!r || !ok) return bad_arg();
+    *ok = 0;
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    if (!frags || !out) return fail(c, DM_ERR_INVALID, "dm_restore_cipher_buffer: null argument");
+    if (nseg == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
+    RC_TRY(process_check(r, size ? size : 1, segment));
+    if (!dm_cipher::segment_ok(segment))
+        return fail(c, DM_ERR_INVALID, "segment size %llu has no room for a block and its padding block",
+                    (unsigned long long)segment);
+    CipherKey key;
+    RC_TRY(cipher_key(c, cipher, cipher_len, key));
+    if (!dm_cipher::size_ok(size, nseg, segment))
+        return fail(c, DM_ERR_INVALID, "size %llu does not end in the last of %llu pieces of %llu bytes",
+                    (unsigned long long)size, (unsigned long long)nseg,
+                    (unsigned long long)(segment - dm_cipher::kBlock));
+    std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
+    const int rc = restore_buffer(r, c->devs[g], frags, frag_names, seg_names, fid, nseg, size, segment, flags, out,
+                                  fst.data(), sst.data(), ok, &key);
     // no copy from the caller's memory stays queued, whichever way the call ends
     if (rc != DM_OK || !*ok) (void)hipStreamSynchronize(c->devs[g].stream);
     if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());

@@ -13,7 +13,7 @@ import ctypes
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
-from ._lib import DM_ERR_EMPTY, DeossMerkleError, load_library
+from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, DeossMerkleError, load_library
 
 
 class MerkleContext:
@@ -196,6 +196,32 @@ class MerkleContext:
         """HBM read-bandwidth probe: XOR of every 8-byte word of dev[0, nbytes) into dev_xor8."""
         self._check(self._L.dm_read_probe_async(self._h, ctypes.c_void_p(dev_ptr), nbytes, ctypes.c_void_p(dev_xor8),
                                                 ctypes.c_void_p(stream or None)), "dm_read_probe_async")
+
+    # -- AES-CBC over device memory (the cipher branch of FullProcessing / Retrievefile) ----------
+    def aes_cbc_encrypt_device_async(self, key: bytes, iv: bytes, dev_ptr: int, stride: int, plain: int,
+                                     nseg: int, stream: int = 0) -> None:
+        """``dm_aes_cbc_encrypt_device_async``: nseg chains in place; segment s's ``plain`` bytes at
+        dev_ptr + s * stride become plain + 16 bytes of ciphertext (PKCS#7 block appended)."""
+        if len(iv) != 16:
+            raise DeossMerkleError(DM_ERR_INVALID, "iv must be 16 bytes")
+        self._check(self._L.dm_aes_cbc_encrypt_device_async(self._h, bytes(key), len(key), bytes(iv),
+                                                            ctypes.c_void_p(dev_ptr), stride, plain, nseg,
+                                                            ctypes.c_void_p(stream or None)),
+                    "dm_aes_cbc_encrypt_device_async")
+
+    def aes_cbc_decrypt_device_async(self, key: bytes, iv: bytes, dev_in: int, in_stride: int, cipher_bytes: int,
+                                     nseg: int, dev_out: int, out_stride: int, dev_pad_ok: int,
+                                     stream: int = 0) -> None:
+        """``dm_aes_cbc_decrypt_device_async``: out of place; cipher_bytes - 16 plaintext bytes per
+        segment at dev_out + s * out_stride, dev_pad_ok[s] = 1 iff the padding block was good."""
+        if len(iv) != 16:
+            raise DeossMerkleError(DM_ERR_INVALID, "iv must be 16 bytes")
+        self._check(self._L.dm_aes_cbc_decrypt_device_async(self._h, bytes(key), len(key), bytes(iv),
+                                                            ctypes.c_void_p(dev_in), in_stride, cipher_bytes, nseg,
+                                                            ctypes.c_void_p(dev_out), out_stride,
+                                                            ctypes.c_void_p(dev_pad_ok),
+                                                            ctypes.c_void_p(stream or None)),
+                    "dm_aes_cbc_decrypt_device_async")
 
     # -- tree levels and proofs (merkletree GetMerklePath / VerifyContent / VerifyTree) ----------
     def tree_node_count(self, n: int) -> int:

@@ -20,7 +20,10 @@ Coding, hashing and the tree run on the GPU; there is no CPU fallback.  Segment 
 too (the zero-padded segment = its data fragments in order), so every returned path exists.
 :meth:`Processor.FullProcessing` is one ``dm_full_processing`` call: the library reads the file,
 and fragment writes overlap the reads and the GPU's hashing.
-Deviation: a non-empty ``cipher`` is rejected (the AES branch is not implemented).
+With a non-empty ``cipher`` the object is AES-CBC encrypted on the GPU first (``dm_process_cipher_buffer``,
+window by window) and everything is named by ciphertext; :meth:`Processor.RestoreFile` with the
+same cipher gives the object back.  The scheme is recalled from the SDK, not pinned against it
+(DESIGN.md §6.14): parity-unpinned, and the Go shim still routes a cipher to the SDK.
 """
 from __future__ import annotations
 
@@ -36,7 +39,14 @@ from .reedsolomon import DATA_SHARDS, PAR_SHARDS, Encoder
 SEGMENT_SIZE = 32 << 20                       # chain.SegmentSize
 FRAGMENT_SIZE = SEGMENT_SIZE // DATA_SHARDS   # chain.FragmentSize (8 MiB; node/tracker.go:250 "96M")
 RESTORE_VERIFY_FRAGMENTS, RESTORE_VERIFY_SEGMENTS, RESTORE_VERIFY_FID, RESTORE_VERIFY_ALL = 1, 2, 4, 7   # DM_RESTORE_*
+CIPHER_BLOCK = 16                             # a piece of segment - 16 plaintext bytes + its PKCS#7 block = one segment
+SEG_BAD_PADDING = 3                           # seg_status of dm_restore_cipher_buffer: what a wrong cipher looks like
 WINDOW_SEGMENTS = 8                           # segments per GPU call (256 MiB of file + 768 MiB of fragments; the Go shim bounds the segments in flight by DEOSS_PROCESS_MEM_GIB)
+
+
+def _cipher_bytes(cipher) -> bytes:
+    """The key bytes of a cipher given as str (a Go string's bytes: UTF-8) or bytes."""
+    return cipher.encode() if isinstance(cipher, str) else bytes(cipher or b"")
 
 
 def _write_segments() -> bool:
@@ -72,10 +82,14 @@ class Processor:
         self.enc._check(rc, what)
 
     # -- raw pipeline ----------------------------------------------------------------------------
-    def process_buffer(self, buf, want_frags: bool = True) -> Tuple[bytes, bytes, bytes, Optional[bytes]]:
-        """One ``dm_process_buffer`` call: (segment digests, fragment digests, fid, fragments)."""
+    def process_buffer(self, buf, want_frags: bool = True, cipher=b"") -> Tuple[bytes, bytes, bytes, Optional[bytes]]:
+        """One ``dm_process_buffer`` call: (segment digests, fragment digests, fid, fragments).  With
+        a ``cipher`` (16, 24 or 32 bytes) one ``dm_process_cipher_buffer`` call: the same over the
+        ceil(len / (segment - 16)) segments of ciphertext."""
         n = len(buf)
-        nseg = (n + self.segment - 1) // self.segment if n else 0
+        key = _cipher_bytes(cipher)
+        piece = self.segment - CIPHER_BLOCK if key else self.segment
+        nseg = (n + piece - 1) // piece if n else 0
         total = self.k + self.m
         seg = ctypes.create_string_buffer(max(32 * nseg, 32))
         frag = ctypes.create_string_buffer(max(32 * nseg * total, 32))
@@ -83,8 +97,12 @@ class Processor:
         frags = ctypes.create_string_buffer(nseg * total * self.frag) if (want_frags and nseg) else None
         src = buf if isinstance(buf, ctypes.Array) else ctypes.create_string_buffer(bytes(buf), max(n, 1))
         L = self.ctx._L
-        self._check(L.dm_process_buffer(self.enc._h, src, n, self.segment, frags, seg, frag, fid),
-                    "dm_process_buffer")
+        if key:
+            self._check(L.dm_process_cipher_buffer(self.enc._h, src, n, self.segment, key, len(key), frags, seg,
+                                                   frag, fid), "dm_process_cipher_buffer")
+        else:
+            self._check(L.dm_process_buffer(self.enc._h, src, n, self.segment, frags, seg, frag, fid),
+                        "dm_process_buffer")
         return seg.raw[:32 * nseg], frag.raw[:32 * nseg * total], fid.raw, (frags.raw if frags is not None else None)
 
     def process_batch(self, bufs, want_frags: bool = False):
@@ -188,13 +206,17 @@ class Processor:
     # -- restore (the download side) ---------------------------------------------------------------
     def restore_buffer(self, frags, size: int, frag_names: Optional[bytes] = None,
                        seg_names: Optional[bytes] = None, fid: Optional[bytes] = None,
-                       flags: int = RESTORE_VERIFY_ALL, out=None) -> Tuple[bool, Optional[bytes], bytes, bytes]:
+                       flags: int = RESTORE_VERIFY_ALL, out=None, cipher=b""
+                       ) -> Tuple[bool, Optional[bytes], bytes, bytes]:
         """``dm_restore_buffer``: the object from fragments in memory.  ``frags``: nseg x (data +
         parity) fragments, flat or one list per segment, ``None`` = not downloaded.  Returns (ok,
         the object's ``size`` bytes or None, fragment statuses, segment statuses); a failed check is
         ``ok = False``, not an exception.  ``out``: a ctypes buffer of ``size`` bytes to fill instead
-        (left untouched unless ok)."""
+        (left untouched unless ok).  With a ``cipher`` (``dm_restore_cipher_buffer``) the names are
+        of ciphertext, ``size`` is the plaintext size, and a segment whose padding block is bad after
+        decryption -- a wrong cipher -- has status ``SEG_BAD_PADDING`` with ``ok = False``."""
         total = self.k + self.m
+        key = _cipher_bytes(cipher)
         flat = [f for seg in frags for f in seg] if frags and isinstance(frags[0], (list, tuple)) else list(frags)
         if len(flat) % total:
             raise DeossMerkleError(DM_ERR_INVALID, "need data + parity entries per segment")
@@ -208,9 +230,14 @@ class Processor:
         fst = ctypes.create_string_buffer(max(nseg * total, 1))
         sst = ctypes.create_string_buffer(max(nseg, 1))
         ok = ctypes.c_int(0)
-        self._check(self.ctx._L.dm_restore_buffer(self.enc._h, ptrs, frag_names, seg_names, fid, nseg, size,
-                                                  self.segment, flags, dst, fst, sst, ctypes.byref(ok)),
-                    "dm_restore_buffer")
+        if key:
+            self._check(self.ctx._L.dm_restore_cipher_buffer(self.enc._h, ptrs, frag_names, seg_names, fid, nseg, size,
+                                                             self.segment, flags, key, len(key), dst, fst, sst,
+                                                             ctypes.byref(ok)), "dm_restore_cipher_buffer")
+        else:
+            self._check(self.ctx._L.dm_restore_buffer(self.enc._h, ptrs, frag_names, seg_names, fid, nseg, size,
+                                                      self.segment, flags, dst, fst, sst, ctypes.byref(ok)),
+                        "dm_restore_buffer")
         data = dst.raw[:size] if (ok.value and out is None) else None
         return bool(ok.value), data, fst.raw[:nseg * total], sst.raw[:nseg]
 
@@ -233,22 +260,57 @@ class Processor:
         self._check(rc, "dm_retrieve_file")
         return bool(ok.value), fst.raw[:nseg * total], sst.raw[:nseg]
 
-    def RestoreFile(self, fragdir: str, segments: List[SegmentDataInfo], size: int, out_path: str
+    def _restore_file_cipher(self, fragdir: str, fragn: bytes, segn: bytes, size: int, out_path: str, key: bytes
+                             ) -> Tuple[bool, bytes, bytes]:
+        """RestoreFile with a cipher: the fragment files that exist (of the right length) are read
+        into memory and restored by one ``dm_restore_cipher_buffer`` call; ``out_path`` is written
+        under a temporary name and renamed only when everything held."""
+        frags = []
+        for i in range(len(fragn) // 32):
+            p = os.path.join(fragdir, fragn[32 * i:32 * i + 32].hex())
+            try:
+                data = open(p, "rb").read() if os.path.getsize(p) == self.frag else None
+            except FileNotFoundError:
+                data = None
+            frags.append(data)
+        ok, data, fst, sst = self.restore_buffer(frags, size, frag_names=fragn, seg_names=segn, cipher=key,
+                                                 flags=RESTORE_VERIFY_FRAGMENTS | RESTORE_VERIFY_SEGMENTS)
+        if ok:
+            tmp = os.path.join(os.path.dirname(out_path), ".dm-rt-%d-%s" % (os.getpid(), os.path.basename(out_path)))
+            try:
+                with open(tmp, "wb") as f:
+                    f.write(data)
+                os.replace(tmp, out_path)
+            except OSError:
+                if os.path.exists(tmp):
+                    os.unlink(tmp)
+                raise
+        return ok, fst, sst
+
+    def RestoreFile(self, fragdir: str, segments: List[SegmentDataInfo], size: int, out_path: str, cipher=""
                     ) -> Tuple[bool, Optional[Exception]]:
         """The RSRestore / join / truncate part of process.Retrievefile: ``segments`` is what
         FullProcessing returned (names = base names of its paths), the fragments are whichever of
         them lie in ``fragdir``.  Every fragment used and every restored segment is checked against
-        its name.  (True, None), or (False, error)."""
+        its name.  With the ``cipher`` the object was processed with, the segments are decrypted
+        after that and ``size`` is the plaintext size.  (True, None), or (False, error)."""
         total = self.k + self.m
+        key = _cipher_bytes(cipher)
         try:
             segn = b"".join(bytes.fromhex(os.path.basename(s.SegmentHash)) for s in segments)
             fragn = b"".join(bytes.fromhex(os.path.basename(f)) for s in segments for f in s.FragmentHash)
             if len(segn) != 32 * len(segments) or len(fragn) != 32 * total * len(segments):
                 raise ValueError("segment and fragment names must be hex SHA-256")
-            ok, fst, sst = self.retrieve_file(fragdir, fragn, size, out_path, seg_names=segn,
-                                              flags=RESTORE_VERIFY_FRAGMENTS | RESTORE_VERIFY_SEGMENTS)
+            if key:
+                ok, fst, sst = self._restore_file_cipher(fragdir, fragn, segn, size, out_path, key)
+            else:
+                ok, fst, sst = self.retrieve_file(fragdir, fragn, size, out_path, seg_names=segn,
+                                                  flags=RESTORE_VERIFY_FRAGMENTS | RESTORE_VERIFY_SEGMENTS)
         except (OSError, ValueError, DeossMerkleError) as e:
             return False, e
+        if not ok and any(st == SEG_BAD_PADDING for st in sst):
+            return False, DeossMerkleError(DM_ERR_INVALID, "restore failed: bad padding after decryption "
+                                           "(wrong cipher?)")
         if not ok:
             bad = [s for s in range(len(sst)) if sst[s]]
             return False, DeossMerkleError(DM_ERR_INVALID, "restore failed: segment(s) %s could not be rebuilt "
@@ -258,9 +320,10 @@ class Processor:
     def FullProcessing(self, file: str, cipher: str, savedir: str
                        ) -> Tuple[Optional[List[SegmentDataInfo]], str, Optional[Exception]]:
         """FullProcessing in one library call (``dm_full_processing``: reads, coding, hashing and
-        fragment writes overlapped)."""
+        fragment writes overlapped).  With a cipher: the window path (FullProcessingWindows), whose
+        every window is one ``dm_process_cipher_buffer`` call."""
         if cipher:
-            return None, "", DeossMerkleError(DM_ERR_INVALID, "cipher is not supported by the GPU pipeline")
+            return self.FullProcessingWindows(file, cipher, savedir)
         try:
             segd, fragd, fid = self.full_processing_file(file, savedir)
         except (OSError, DeossMerkleError) as e:
@@ -281,9 +344,10 @@ class Processor:
                               ) -> Tuple[Optional[List[SegmentDataInfo]], str, Optional[Exception]]:
         """The window path (the Go shim's shape before dm_full_processing): read a window of
         ``WINDOW_SEGMENTS`` segments, one ``dm_process_buffer`` call, write its fragments, repeat.
-        Kept as the A/B baseline of ``bench.py --workload fullprocessing``."""
-        if cipher:
-            return None, "", DeossMerkleError(DM_ERR_INVALID, "cipher is not supported by the GPU pipeline")
+        Kept as the A/B baseline of ``bench.py --workload fullprocessing``.  With a cipher a window
+        is ``WINDOW_SEGMENTS`` pieces of ``segment - 16`` plaintext bytes (segments are independent
+        CBC chains, so windows carry no state) and the fid is the tree over all segment digests."""
+        key = _cipher_bytes(cipher)
         try:
             size = os.path.getsize(file)
         except OSError as e:
@@ -293,7 +357,7 @@ class Processor:
         os.makedirs(savedir, exist_ok=True)
         info: List[SegmentDataInfo] = []
         seg_digests = []
-        window = WINDOW_SEGMENTS * self.segment
+        window = WINDOW_SEGMENTS * (self.segment - CIPHER_BLOCK if key else self.segment)
         total = self.k + self.m
         try:
             with open(file, "rb") as f:
@@ -301,7 +365,7 @@ class Processor:
                     buf = f.read(window)
                     if not buf:
                         break
-                    segd, fragd, fid, frags = self.process_buffer(buf, want_frags=True)
+                    segd, fragd, fid, frags = self.process_buffer(buf, want_frags=True, cipher=key)
                     for s in range(len(segd) // 32):
                         seg_digests.append(segd[32 * s:32 * s + 32])
                         names = []
@@ -321,7 +385,7 @@ class Processor:
                         break
         except (OSError, DeossMerkleError) as e:
             return None, "", e
-        if len(seg_digests) * self.segment > window:   # several windows: tree over all segments
+        if len(seg_digests) > WINDOW_SEGMENTS:   # several windows: tree over all segments
             fid = self.ctx.tree_root(b"".join(seg_digests))
         return info, fid.hex(), None
 
@@ -435,7 +499,7 @@ def FullProcessing(file: str, cipher: str, savedir: str
     return _default.FullProcessing(file, cipher, savedir)
 
 
-def RestoreFile(fragdir: str, segments: List[SegmentDataInfo], size: int, out_path: str
+def RestoreFile(fragdir: str, segments: List[SegmentDataInfo], size: int, out_path: str, cipher=""
                 ) -> Tuple[bool, Optional[Exception]]:
     """The restore part of process.Retrievefile on the default GPU pipeline (Processor.RestoreFile)."""
     global _default
@@ -444,7 +508,7 @@ def RestoreFile(fragdir: str, segments: List[SegmentDataInfo], size: int, out_pa
             _default = Processor()
         except DeossMerkleError as e:   # no GPU: fails the Go way, as FullProcessing
             return False, e
-    return _default.RestoreFile(fragdir, segments, size, out_path)
+    return _default.RestoreFile(fragdir, segments, size, out_path, cipher)
 
 
 def FindFragment(fpath: str, fragment_hash: str) -> Tuple[Optional[bytes], Optional[Exception]]:

@@ -224,7 +224,8 @@ int dm_rs_reconstruct_device_async(dm_rs *rs, void *const *shards, const uint8_t
  * is named by its SHA-256 (its file name in savedir is the hex digest); the fid is the
  * common/hashtree root over the segments (NewHashTree(segmentPaths), types.go:19-39).  Coding,
  * hashing and the tree all run on the GPU.  Empty object -> DM_ERR_EMPTY.  The cipher branch
- * (AES before coding) is not implemented. */
+ * (AES-CBC before coding) is dm_process_cipher_buffer / dm_restore_cipher_buffer below; its scheme
+ * is recalled from the SDK, not pinned against it. */
 
 /* Device-resident form on rs's context.  dev_obj holds len bytes with room for nseg * segment
  * (nseg = ceil(len / segment)); the padding [len, nseg * segment) is zeroed in place.  segment must
@@ -327,6 +328,47 @@ int dm_restore_buffer(dm_rs *rs, const void *const *frags, const uint8_t *frag_n
 int dm_retrieve_file(dm_rs *rs, const char *fragdir, const uint8_t *frag_names, const uint8_t *seg_names,
                      const uint8_t *fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
                      const char *out_path, uint8_t *frag_status, uint8_t *seg_status, int *ok);
+
+/* ---- the cipher branch: FullProcessing(file, cipher != "", savedir) and Retrievefile(..., cipher)
+ * PARITY-UNPINNED: the scheme is restated from recollection of cess-go-sdk core/process and
+ * utils.AesCbcEncrypt / AesCbcDecrypt (deoss_amd/csrc/cipher_scheme.hpp); the
+ * AES-CBC core is pinned by FIPS-197 and SP 800-38A vectors.  Key = the cipher's bytes (16, 24 or 32:
+ * AES-128 / -192 / -256; any other length is DM_ERR_INVALID "cipher must be 16, 24 or 32 bytes"),
+ * IV = its first 16 bytes, the same for every segment.  The object is cut into pieces of
+ * P = segment - 16 plaintext bytes (the last zero-padded to P); a piece CBC-encrypted with PKCS#7
+ * padding (always one block of sixteen 0x10 bytes) is exactly one segment of ciphertext, and coding,
+ * names and fid are of the ciphertext: nseg = ceil(len / P).
+ *
+ * AES-CBC over device memory, nseg independent chains with one key and one IV, on `stream`.
+ * Encrypt works in place: segment s holds `plain` plaintext bytes at dev + s*stride and gets
+ * plain + 16 bytes of ciphertext there (the padding block appended).  plain % 16 == 0,
+ * plain + 16 <= stride, dev and stride 16-byte aligned.  One serial chain per segment: a throughput
+ * path (many segments side by side). */
+int dm_aes_cbc_encrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16], void *dev,
+                                    uint64_t stride, uint64_t plain, uint64_t nseg, void *stream);
+/* Decrypt works out of place (the two buffers must not overlap): segment s's cipher_bytes at
+ * dev_in + s*in_stride become cipher_bytes - 16 plaintext bytes at dev_out + s*out_stride (with
+ * out_stride = cipher_bytes - 16 the output is the joined object), and dev_pad_ok[s] (one byte per
+ * segment) is 1 iff its last block decrypts to sixteen 0x10 bytes, else 0.  cipher_bytes % 16 == 0,
+ * cipher_bytes >= 32; buffers and strides 16-byte aligned. */
+int dm_aes_cbc_decrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16],
+                                    const void *dev_in, uint64_t in_stride, uint64_t cipher_bytes, uint64_t nseg,
+                                    void *dev_out, uint64_t out_stride, void *dev_pad_ok, void *stream);
+/* dm_process_buffer with a cipher (synchronous): outputs as there, over nseg = ceil(len / (segment - 16))
+ * segments of ciphertext. */
+int dm_process_cipher_buffer(dm_rs *rs, const void *host, uint64_t len, uint64_t segment, const void *cipher,
+                             uint64_t cipher_len, void *frags_out, uint8_t *seg_hashes, uint8_t *frag_hashes,
+                             uint8_t fid[32]);
+/* dm_restore_buffer with a cipher: the verified restore as there (every name and the fid are of
+ * ciphertext), then every segment is decrypted and its padding block checked.  `size` is the
+ * plaintext size, (nseg-1)*(segment-16) < size <= nseg*(segment-16).  A bad padding block -- what a
+ * wrong cipher looks like -- sets seg_status[s] = 3 and *ok = 0: a result, not an error, and `out`
+ * stays untouched.  Bytes leave the device only when every check asked for held and every padding
+ * was good. */
+int dm_restore_cipher_buffer(dm_rs *rs, const void *const *frags, const uint8_t *frag_names, const uint8_t *seg_names,
+                             const uint8_t *fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
+                             const void *cipher, uint64_t cipher_len, void *out, uint8_t *frag_status,
+                             uint8_t *seg_status, int *ok);
 
 /* FullProcessing while the upload body arrives (SURVEY.md 8f #1 + #2): the handlers write the body
  * to a file (node/objectHandler.go:248-266, node/fileHandler.go:899-937) and then run

@@ -4,11 +4,14 @@
 // node/tracker.go:767-769) and the streaming Writer (go/process/stream_hip.go), over the C ABI
 // (include/deoss_merkle.h: dm_full_processing, dm_pstream_*).  Same result shape: segment and
 // fragment path names under savedir (every one exists as a file), the hex fid, an error.
-// Deviation (as in Go): a non-empty cipher is an error.  Header-only; link -ldeoss_merkle.
+// A non-empty cipher takes the window path over dm_process_cipher_buffer (the scheme is recalled
+// from the SDK, parity-unpinned: DESIGN.md §6.14; the Go shim still routes a cipher to the SDK).
+// Header-only; link -ldeoss_merkle.
 #pragma once
 
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <memory>
 #include <optional>
@@ -16,6 +19,8 @@
 #include <tuple>
 #include <utility>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "deoss_merkle.h"
 
@@ -45,6 +50,12 @@ class Pipelines {
         return p;
     }
     dm_rs* pick() { return rs_.empty() ? nullptr : rs_[next_++ % rs_.size()]; }
+    // a coder and the context it lives on (the cipher window path reduces the fid on it)
+    std::pair<dm_rs*, dm_ctx*> pick_pair() {
+        if (rs_.empty()) return {nullptr, nullptr};
+        const size_t i = next_++ % rs_.size();
+        return {rs_[i], ctx_[i]};
+    }
     int status() const { return rc_; }
     ~Pipelines() {
         for (dm_rs* r : rs_) dm_rs_destroy(r);
@@ -106,10 +117,84 @@ inline std::vector<SegmentDataInfo> infos(const std::string& savedir, const std:
     return out;
 }
 
+constexpr uint64_t WindowSegments = 8;   // segments per dm_process_cipher_buffer call (the cipher window path)
+
+inline std::optional<Error> write_new(const std::string& path, const uint8_t* p, uint64_t n) {
+    if (FILE* have = std::fopen(path.c_str(), "rb")) {   // named by content: an existing file is this one
+        std::fclose(have);
+        return std::nullopt;
+    }
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return Error{DM_ERR_IO, "open " + path + ": cannot create"};
+    const bool ok = std::fwrite(p, 1, n, f) == n;
+    if (std::fclose(f) != 0 || !ok) return Error{DM_ERR_IO, "write " + path + ": short write"};
+    return std::nullopt;
+}
+
+// FullProcessing(file, cipher != "", savedir): the window path.  The file is read in windows of
+// WindowSegments pieces of segment - 16 plaintext bytes; each window is one
+// dm_process_cipher_buffer call (AES-CBC, coding and names on the GPU; segments are independent
+// chains, so windows carry no state), its fragment and segment files are written, and the fid is
+// the tree over all segment digests.  PARITY-UNPINNED: the scheme is recalled from the SDK
+// (deoss_merkle.h).  `segment` is chain.SegmentSize outside tests.
+inline Result FullProcessingCipher(const std::string& file, const std::string& cipher, const std::string& savedir,
+                                   uint64_t segment = SegmentSize) {
+    auto& p = Pipelines::instance();
+    auto [rs, ctx] = p.pick_pair();
+    if (!rs) return {{}, "", Error{p.status(), dm_strerror(p.status())}};
+    if (segment <= 16) return {{}, "", Error{DM_ERR_INVALID, "process: segment too small for a cipher"}};
+    FILE* f = std::fopen(file.c_str(), "rb");
+    if (!f) return {{}, "", Error{DM_ERR_IO, "open " + file + ": no such file or directory"}};
+    (void)::mkdir(savedir.c_str(), 0777);   // as the library's file path: savedir may not exist yet
+    const int total = DataShards + ParShards;
+    const uint64_t piece = segment - 16, frag = segment / DataShards, window = WindowSegments * piece;
+    const bool segfiles = write_segments();
+    std::vector<uint8_t> buf(window), segd_all, fragd_all, frags;
+    std::optional<Error> err;
+    uint8_t fid[32] = {};
+    uint64_t nseg_all = 0, calls = 0;
+    for (;;) {
+        const uint64_t got = std::fread(buf.data(), 1, window, f);
+        if (got == 0) break;
+        const uint64_t ns = (got + piece - 1) / piece;
+        segd_all.resize(32 * (nseg_all + ns));
+        fragd_all.resize(32 * (nseg_all + ns) * total);
+        frags.resize(ns * total * frag);
+        uint8_t* segd = segd_all.data() + 32 * nseg_all;
+        uint8_t* fragd = fragd_all.data() + 32 * nseg_all * total;
+        const int rc = dm_process_cipher_buffer(rs, buf.data(), got, segment, cipher.data(), cipher.size(), frags.data(),
+                                                segd, fragd, fid);
+        if (rc != DM_OK) {
+            err = last_error(rc);
+            break;
+        }
+        calls++;
+        for (uint64_t s = 0; s < ns && !err; s++) {
+            for (int j = 0; j < total && !err; j++)
+                err = write_new(join(savedir, hex32(fragd + 32 * (s * total + j))), frags.data() + (s * total + j) * frag, frag);
+            // data fragments in order = the segment's ciphertext
+            if (segfiles && !err) err = write_new(join(savedir, hex32(segd + 32 * s)), frags.data() + s * total * frag, segment);
+        }
+        nseg_all += ns;
+        if (err || got < window) break;
+    }
+    std::fclose(f);
+    if (err) return {{}, "", err};
+    if (nseg_all == 0) return {{}, "", Error{DM_ERR_EMPTY, "Empty data"}};
+    if (calls > 1) {   // several windows: the tree over all segment digests
+        std::vector<uint8_t> nodes(32 * dm_tree_node_count(nseg_all));
+        const int rc = dm_tree_levels(ctx, segd_all.data(), nseg_all, nodes.data());
+        if (rc != DM_OK) return {{}, "", last_error(rc)};
+        std::copy(nodes.end() - 32, nodes.end(), fid);
+    }
+    return {infos(savedir, segd_all, fragd_all, nseg_all), hex32(fid), std::nullopt};
+}
+
 // FullProcessing(file, cipher, savedir): one dm_full_processing call (the library reads the file
-// and writes every fragment and segment file to savedir/<hex SHA-256>).
+// and writes every fragment and segment file to savedir/<hex SHA-256>); with a cipher, the window
+// path over dm_process_cipher_buffer (FullProcessingCipher).
 inline Result FullProcessing(const std::string& file, const std::string& cipher, const std::string& savedir) {
-    if (!cipher.empty()) return {{}, "", Error{DM_ERR_INVALID, "process: cipher is not supported by the GPU pipeline"}};
+    if (!cipher.empty()) return FullProcessingCipher(file, cipher, savedir);
     auto& p = Pipelines::instance();
     dm_rs* rs = p.pick();
     if (!rs) return {{}, "", Error{p.status(), dm_strerror(p.status())}};
