@@ -1,8 +1,8 @@
 // fp_files.hpp -- the files a FullProcessing call writes (pure host code: POSIX only, no HIP).
 //
 // Shared by dm_full_processing (fullproc_capi.inl), the processing stream (process_stream.inl),
-// dm_fragment_lookup and the restore path (Go-style error texts, FdGuard, env_bytes), and by the
-// host tests (tests/cpp/test_fp_files.cpp, plain and ASan/UBSan, no GPU).
+// dm_fragment_lookup and the restore path (its fragment reads and output writes, Go-style error
+// texts, FdGuard, env_bytes), and by the host tests (tests/cpp/test_fp_files.cpp, plain and ASan/UBSan, no GPU).
 //
 // Every output file is written under a temporary name in the save directory while the GPU still
 // hashes it, and renamed to <hex SHA-256> once its digest is back (FpOutputs).  Error texts are
@@ -179,6 +179,53 @@ struct SlotWrites {
     }
     ~SlotWrites() { (void)wait(); }
 };
+
+// The restore path's reads: file i of `paths` (len bytes each) to buf + i * len, up to `readers`
+// files at a time; the first error ("open P: ...", "read P: ...", "read P: unexpected EOF" for a
+// short file) once every reader has finished, "" on success.  (Tested in tests/cpp/test_rs_plan.cpp.)
+inline std::string read_files(const std::string* paths, size_t n, uint64_t len, uint8_t* buf, size_t readers) {
+    const size_t J = std::min(readers, n);
+    std::vector<std::future<std::string>> jobs;
+    for (size_t j = 0; j < J; j++)
+        jobs.push_back(std::async(std::launch::async, [=]() -> std::string {
+            for (size_t i = j; i < n; i += J) {
+                const std::string& p = paths[i];
+                const int fd = ::open(p.c_str(), O_RDONLY | O_CLOEXEC);
+                if (fd < 0) return "open " + p + ": " + go_errno(errno);
+                uint64_t done = 0;
+                while (done < len) {
+                    const ssize_t got = ::pread(fd, buf + i * len + done, len - done, (off_t)done);
+                    if (got < 0 && errno == EINTR) continue;
+                    if (got <= 0) {
+                        const std::string e = got < 0 ? go_errno(errno) : std::string("unexpected EOF");
+                        ::close(fd);
+                        return "read " + p + ": " + e;
+                    }
+                    done += (uint64_t)got;
+                }
+                ::close(fd);
+            }
+            return std::string();
+        }));
+    std::string err;
+    for (auto& j : jobs) {
+        const std::string e = j.get();
+        if (err.empty()) err = e;
+    }
+    return err;
+}
+
+// len bytes to [off, off + len) of the open file fd (`path` names it in the error); "" on success.
+inline std::string pwrite_all(int fd, const std::string& path, const uint8_t* p, uint64_t len, uint64_t off) {
+    uint64_t done = 0;
+    while (done < len) {
+        const ssize_t w = ::pwrite(fd, p + done, len - done, (off_t)(off + done));
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) return "write " + path + ": " + go_errno(w < 0 ? errno : EIO);
+        done += (uint64_t)w;
+    }
+    return "";
+}
 
 inline std::atomic<uint64_t> g_fp_seq{0};   // one counter for every call's temporary names
 

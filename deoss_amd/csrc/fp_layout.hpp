@@ -1,8 +1,9 @@
 // fp_layout.hpp -- where the segments, fragments and digests of a FullProcessing pass live (pure
 // host code, no HIP).
 //
-// Shared by every path built on the FullProcessing pass (process_capi.inl, fullproc_capi.inl,
-// process_stream.inl, fragment_capi.inl, restore_capi.inl) and by the host tests
+// Shared by every path built on the FullProcessing pass (process_capi.inl -- process_staged with a
+// cipher or without --, fullproc_capi.inl, process_stream.inl, fragment_capi.inl, and the windows
+// of restore_capi.inl) and by the host tests
 // (tests/cpp/test_fp_layout.cpp, plain and ASan/UBSan, no GPU).
 //
 // A segment of `seg` bytes is k data fragments of frag = seg / k bytes -- slices of the segment

@@ -103,28 +103,28 @@ int process_staged(dm_rs* r, Dev& d, const std::vector<uint64_t>& first, uint64_
                    uint8_t* const* seg_hashes, uint8_t* const* frag_hashes, uint8_t* fids) {
     dm_ctx* c = r->c;
     hipStream_t s = d.stream;
-    const int k = r->k, m = r->m, total = k + m;
-    const uint64_t frag = segment / (uint64_t)k;
+    const FpLayout L(r->k, r->m, segment);
     const uint64_t nobj = first.size() - 1, S = first[nobj];
     DevBuf& work = rs_ln(r, d).work;
-    HIP_TRY(work.ensure(S * (uint64_t)m * frag + nobj * 32));
+    HIP_TRY(work.ensure(S * L.pbytes + nobj * 32));
     uint8_t* parity = work.u8();
-    uint8_t* dfid = parity + S * (uint64_t)m * frag;
+    uint8_t* dfid = parity + S * L.pbytes;
     RC_TRY(process_segments(r, d, s, d.data.u8(), segment, parity, first, dfid));
     HIP_TRY(hipMemcpyAsync(fids, dfid, nobj * 32, hipMemcpyDeviceToHost, s));
+    const uint64_t set = (uint64_t)L.total * L.frag;   // a segment's fragments in frags_out: data, then parity
     for (uint64_t o = 0; o < nobj; o++) {
         const uint64_t f0 = first[o], ns = first[o + 1] - first[o];
         if (seg_hashes && seg_hashes[o])
-            HIP_TRY(hipMemcpyAsync(seg_hashes[o], d.leaves.u8() + f0 * 32, ns * 32, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(seg_hashes[o], d.leaves.u8() + 32 * L.seg_slot(f0), ns * 32, hipMemcpyDeviceToHost, s));
         if (frag_hashes && frag_hashes[o])
-            HIP_TRY(hipMemcpyAsync(frag_hashes[o], d.leaves.u8() + (S + f0 * total) * 32, ns * total * 32,
+            HIP_TRY(hipMemcpyAsync(frag_hashes[o], d.leaves.u8() + 32 * L.frag_slot(S, f0, 0), ns * L.total * 32,
                                    hipMemcpyDeviceToHost, s));
         if (frags_out && frags_out[o]) {
             uint8_t* out = static_cast<uint8_t*>(frags_out[o]);
             for (uint64_t i = 0; i < ns; i++) {
-                HIP_TRY(hipMemcpyAsync(out + i * total * frag, d.data.u8() + (f0 + i) * segment, segment,
+                HIP_TRY(hipMemcpyAsync(out + i * set, L.frag_ptr(d.data.u8(), parity, f0 + i, 0), L.seg,
                                        hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipMemcpyAsync(out + i * total * frag + segment, parity + (f0 + i) * m * frag, m * frag,
+                HIP_TRY(hipMemcpyAsync(out + i * set + L.seg, L.frag_ptr(d.data.u8(), parity, f0 + i, L.k), L.pbytes,
                                        hipMemcpyDeviceToHost, s));
             }
         }

@@ -1,6 +1,7 @@
 // restore_capi.inl -- the download side on the GPU (dm_rs_restore_*, dm_restore_buffer,
 // dm_retrieve_file; include/deoss_merkle.h).  Part of merkle_capi.hip (after fullproc_capi.inl;
-// shares dm_ctx, Dev, dm_rs, the leaf launches and the file helpers).
+// shares dm_ctx, Dev, dm_rs and the leaf launches).  Plans, statuses and a launch's descriptors are
+// rs_plan.hpp; the fragment reads and the output writes are fp_files.hpp (read_files, pwrite_all).
 //
 // Replaces the RSRestore / join / truncate part of cess-go-sdk process.Retrievefile(chainer, fmeta,
 // fid, dir, cipher = "") (node/fileHandler.go:519,600,990): for every segment any chain.DataShards
@@ -15,97 +16,13 @@
 //   4. (DM_RESTORE_VERIFY_SEGMENTS / _FID) one leaf launch hashes the restored segments, the
 //      digests reduce to the fid;
 //   5. the object's bytes leave the device only when everything asked for held.
+// Steps 2 - 4 are rt_check_frags and rt_rebuild for both paths; they take addresses, and each path
+// keeps its own layout of the parity fragments and its own policy after a failed check.
 
 namespace {
 
 constexpr uint64_t kRtWindowBytes = 1ull << 30;   // dm_retrieve_file: segment bytes per GPU pass (+ 2x parity scratch)
 constexpr int kRtReaders = 8;                      // fragment files read at once into a pinned slot
-
-struct RestorePlan {
-    int inputs[dm::kRsMaxIn];
-    int outputs[dm::kRsMaxIn];
-    int nout = 0;
-    uint8_t rows[dm::kRsMaxIn * dm::kRsMaxIn];   // nout x k
-};
-
-// The plan of one pattern (klauspost's rule, as rs_decode_plan): the first k present fragments in
-// index order are read; every data fragment that is missing or not at its final address is
-// written, fragment j with row j of the inverse of the inputs' sub-matrix (a unit row when j is
-// itself an input: a present data fragment always is).
-int restore_plan(dm_ctx* c, const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* in_place,
-                 RestorePlan& p) {
-    const int total = k + m;
-    int nv = 0;
-    for (int i = 0; i < total && nv < k; i++)
-        if (present[i]) p.inputs[nv++] = i;
-    if (nv < k) return fail(c, DM_ERR_INVALID, "too few shards given (%d of %d needed)", nv, k);
-    uint8_t sub[dm::kRsMaxIn * dm::kRsMaxIn], inv[dm::kRsMaxIn * dm::kRsMaxIn];
-    for (int i = 0; i < k; i++) std::memcpy(sub + i * k, mat + p.inputs[i] * k, (size_t)k);
-    if (!gf_invert(sub, k, inv)) return fail(c, DM_ERR_INVALID, "singular decode matrix");
-    p.nout = 0;
-    for (int j = 0; j < k; j++) {
-        if (present[j] && in_place && in_place[j]) continue;
-        p.outputs[p.nout] = j;
-        std::memcpy(p.rows + p.nout * k, inv + j * k, (size_t)k);
-        p.nout++;
-    }
-    return DM_OK;
-}
-
-// Descriptors and coding tables of one restore launch, built segment by segment.
-struct RestoreBatch {
-    struct Cached {
-        RestorePlan p;
-        uint32_t tab;
-    };
-    std::vector<dm::RsRestoreDesc> desc;
-    std::vector<uint64_t> tabs;                 // [ntab][k][256]
-    std::map<uint32_t, Cached> plans;           // present mask | in-place mask << 16
-    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index (one table per distinct plan)
-    bool any_out = false;
-};
-
-// Segment whose usable fragments are frags[0 .. total) (device addresses, NULL = absent) and whose
-// data fragment j belongs at seg_base + j * frag.
-int restore_add(dm_rs* r, RestoreBatch& b, const uint8_t* const* frags, uint8_t* seg_base, uint64_t frag) {
-    const int k = r->k, total = r->k + r->m;
-    uint8_t present[dm::kRsMaxIn + dm::kRsMaxOut], in_place[dm::kRsMaxIn];
-    uint32_t key = 0;
-    for (int j = 0; j < total; j++) {
-        present[j] = frags[j] != nullptr;
-        key |= (uint32_t)present[j] << j;
-        if (j < k) {
-            in_place[j] = frags[j] == seg_base + (uint64_t)j * frag;
-            key |= (uint32_t)in_place[j] << (16 + j);
-        }
-    }
-    auto it = b.plans.find(key);
-    if (it == b.plans.end()) {
-        RestoreBatch::Cached cp;
-        RC_TRY(restore_plan(r->c, r->mat.data(), k, r->m, present, in_place, cp.p));
-        cp.tab = 0;
-        if (cp.p.nout) {
-            const std::string rows(reinterpret_cast<const char*>(cp.p.rows), (size_t)cp.p.nout * k);
-            auto t = b.tab_of.find(rows);
-            if (t == b.tab_of.end()) {
-                const std::vector<uint64_t> tab = rs_table(cp.p.rows, cp.p.nout, k);
-                t = b.tab_of.emplace(rows, (uint32_t)(b.tabs.size() / ((size_t)k * 256))).first;
-                b.tabs.insert(b.tabs.end(), tab.begin(), tab.end());
-            }
-            cp.tab = t->second;
-        }
-        it = b.plans.emplace(key, cp).first;
-    }
-    const RestorePlan& p = it->second.p;
-    dm::RsRestoreDesc ds{};
-    for (int j = 0; j < k; j++) ds.in[j] = frags[p.inputs[j]];
-    for (int i = 0; i < p.nout; i++) ds.out[i] = seg_base + (uint64_t)p.outputs[i] * frag;
-    ds.nout = (uint32_t)p.nout;
-    ds.table = it->second.tab;
-    if (p.nout) b.any_out = true;
-    b.desc.push_back(ds);
-    return DM_OK;
-}
 
 int restore_launch(dm_rs* r, Dev& d, hipStream_t s, const RestoreBatch& b, uint64_t units) {
     dm_ctx* c = r->c;
@@ -142,39 +59,98 @@ int rt_hash(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<uint64_t>& addrs
     return DM_OK;
 }
 
-enum : uint8_t { kFragAbsent = 0, kFragUsed = 1, kFragSpare = 2, kFragBad = 3 };
-enum : uint8_t { kSegOk = 0, kSegTooFew = 1, kSegMismatch = 2, kSegBadPadding = 3 };
+// The fragments of a run of segments, [ns * total]: where one that is on the device and passed its
+// check lies, else null.
+using RtFrags = std::vector<const uint8_t*>;
 
-// Fragment states of ns segments -> statuses: the first k good fragments of a segment are used, the
-// other good ones spare; a segment with fewer than k good ones is kSegTooFew (its good fragments
-// stay spare: nothing is rebuilt from them).  `good` holds 1 for a fragment that is on the device
-// and passed its check.  Returns false when any segment has too few.
-bool rt_select(int k, int total, uint64_t ns, const uint8_t* good, uint8_t* fst, uint8_t* sst) {
-    bool all = true;
-    for (uint64_t t = 0; t < ns; t++) {
-        int ng = 0;
-        for (int j = 0; j < total; j++) ng += good[t * total + j];
-        const bool enough = ng >= k;
-        if (!enough) {
-            sst[t] = kSegTooFew;
-            all = false;
-        }
-        int used = 0;
-        for (int j = 0; j < total; j++)
-            if (good[t * total + j]) fst[t * total + j] = (enough && used++ < k) ? kFragUsed : kFragSpare;
+struct RtLoad {     // one fragment brought to the device
+    uint64_t idx;   // t * total + j within the run
+    uint8_t* to;
+};
+
+// 2. The fragments just loaded against their names (names + 32 * idx; null: taken as given), hashed
+// in one leaf launch: a good one is entered in f, another is kFragBad.
+int rt_check_frags(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<RtLoad>& loads, uint64_t frag,
+                   const uint8_t* names, RtFrags& f, uint8_t* fst) {
+    std::vector<uint8_t> dig;
+    if (names) {
+        std::vector<uint64_t> addrs(loads.size());
+        for (size_t q = 0; q < loads.size(); q++) addrs[q] = reinterpret_cast<uint64_t>(loads[q].to);
+        RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
     }
-    return all;
+    for (size_t q = 0; q < loads.size(); q++) {
+        const uint64_t i = loads[q].idx;
+        if (names && std::memcmp(dig.data() + 32 * q, names + 32 * i, 32) != 0) {
+            fst[i] = kFragBad;
+            continue;
+        }
+        f[i] = loads[q].to;
+    }
+    return DM_OK;
 }
 
-int restore_check(dm_rs* r, uint64_t nseg, uint64_t size, uint64_t segment) {
+enum class Rebuild { kDone, kTooFew, kMismatch };
+
+// 3 + 4. ns segments at `base` from the good fragments, wherever those lie: statuses (kTooFew:
+// nothing is launched), ONE restore launch; then, with seg_names or want_segd, one leaf launch over
+// the segments, whose digests go to segd and are compared with seg_names (nullable; kMismatch).
+int rt_rebuild(dm_rs* r, Dev& d, hipStream_t s, const RtFrags& f, uint64_t ns, uint8_t* base, uint64_t segment,
+               uint8_t* fst, uint8_t* sst, const uint8_t* seg_names, bool want_segd, std::vector<uint8_t>& segd,
+               Rebuild& res) {
+    dm_ctx* c = r->c;
+    const int k = r->k, total = r->k + r->m;
+    const uint64_t frag = segment / (uint64_t)k;
+    res = Rebuild::kTooFew;
+    if (!rt_select(k, total, ns, f.data(), fst, sst)) return DM_OK;
+    RestoreBatch b{r->mat.data(), k, r->m};
+    for (uint64_t t = 0; t < ns; t++)
+        RC_TRY(plan_status(c, restore_add(b, f.data() + t * total, base + t * segment, frag), k));
+    RC_TRY(restore_launch(r, d, s, b, frag / 16));
+    res = Rebuild::kDone;
+    if (!seg_names && !want_segd) return DM_OK;
+    std::vector<uint64_t> sa(ns);
+    for (uint64_t t = 0; t < ns; t++) sa[t] = reinterpret_cast<uint64_t>(base + t * segment);
+    RC_TRY(rt_hash(c, d, s, sa, segment, segd));
+    if (seg_names)
+        for (uint64_t t = 0; t < ns; t++)
+            if (std::memcmp(segd.data() + 32 * t, seg_names + 32 * t, 32) != 0) {
+                sst[t] = kSegMismatch;
+                res = Rebuild::kMismatch;
+            }
+    return DM_OK;
+}
+
+// The arguments every restore entry point shares.  key (nullable): the call has a cipher, which is
+// parsed into it; the object then ends in the last of nseg pieces of segment - 16 bytes.
+int restore_check(dm_rs* r, uint64_t nseg, uint64_t size, uint64_t segment, CipherKey* key = nullptr,
+                  const void* cipher = nullptr, uint64_t cipher_len = 0) {
     dm_ctx* c = r->c;
     if (nseg == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
     RC_TRY(process_check(r, size ? size : 1, segment));
-    if (size <= (nseg - 1) * segment || size > nseg * segment)
-        return fail(c, DM_ERR_INVALID, "size %llu does not end in the last of %llu segments of %llu bytes",
-                    (unsigned long long)size, (unsigned long long)nseg, (unsigned long long)segment);
+    uint64_t piece = segment;
+    if (key) {
+        if (!dm_cipher::segment_ok(segment))
+            return fail(c, DM_ERR_INVALID, "segment size %llu has no room for a block and its padding block",
+                        (unsigned long long)segment);
+        RC_TRY(cipher_key(c, cipher, cipher_len, *key));
+        piece = segment - dm_cipher::kBlock;
+    }
+    if (size <= (nseg - 1) * piece || size > nseg * piece)
+        return fail(c, DM_ERR_INVALID, "size %llu does not end in the last of %llu %s of %llu bytes",
+                    (unsigned long long)size, (unsigned long long)nseg, key ? "pieces" : "segments",
+                    (unsigned long long)piece);
     return DM_OK;
 }
+
+// The fragment and segment statuses of a call, copied to the caller however the call ends.
+struct RtStatus {
+    std::vector<uint8_t> fst, sst;
+    RtStatus(const dm_rs* r, uint64_t nseg) : fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0) {}
+    void copy_out(uint8_t* frag_status, uint8_t* seg_status) const {
+        if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
+        if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
+    }
+};
 
 // key (nullable): the object was uploaded with a cipher (cipher_scheme.hpp).  Every name and the
 // fid are of ciphertext, so steps 1-4 run as without one; then the segments are decrypted into
@@ -197,63 +173,34 @@ int restore_buffer(dm_rs* r, Dev& d, const void* const* frags, const uint8_t* fr
     // with a cipher: the plaintext pieces and the padding verdicts follow the parity fragments
     const uint64_t piece = segment - dm_cipher::kBlock, plain_off = round_up(npar * frag + 16, kAlign);
     HIP_TRY(work.ensure(key ? plain_off + nseg * piece + nseg : npar * frag + 16));
-    std::vector<const uint8_t*> dev(NF, nullptr);
-    std::vector<uint8_t> good(NF, 0);
-    std::vector<uint64_t> addrs, which;
-    uint64_t slot = 0;
+    RtFrags have(NF, nullptr);
+    std::vector<RtLoad> loads;
+    uint64_t slot = 0;   // parity fragments are packed: only those given take room
     for (uint64_t t = 0; t < nseg; t++)
         for (int j = 0; j < total; j++) {
             const uint64_t i = t * total + j;
             if (!frags[i]) continue;
             uint8_t* to = j < k ? d.data.u8() + t * segment + (uint64_t)j * frag : work.u8() + (slot++) * frag;
             HIP_TRY(hipMemcpyAsync(to, frags[i], frag, hipMemcpyHostToDevice, s));
-            dev[i] = to;
-            good[i] = 1;
-            addrs.push_back(reinterpret_cast<uint64_t>(to));
-            which.push_back(i);
+            loads.push_back({i, to});
         }
     // 2. every supplied fragment against its name
-    if ((flags & DM_RESTORE_VERIFY_FRAGMENTS) && frag_names) {
-        std::vector<uint8_t> dig;
-        RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
-        for (size_t q = 0; q < which.size(); q++)
-            if (std::memcmp(dig.data() + 32 * q, frag_names + 32 * which[q], 32) != 0) {
-                good[which[q]] = 0;
-                fst[which[q]] = kFragBad;
-            }
-    }
-    // 3. plans from the good set, one restore launch
-    if (!rt_select(k, total, nseg, good.data(), fst, sst)) return DM_OK;
-    RestoreBatch b;
-    std::vector<const uint8_t*> use((size_t)total);
-    for (uint64_t t = 0; t < nseg; t++) {
-        for (int j = 0; j < total; j++) use[j] = good[t * total + j] ? dev[t * total + j] : nullptr;
-        RC_TRY(restore_add(r, b, use.data(), d.data.u8() + t * segment, frag));
-    }
-    RC_TRY(restore_launch(r, d, s, b, frag / 16));
-    // 4. the restored segments against their names, their tree against the fid
+    const bool vfrag = (flags & DM_RESTORE_VERIFY_FRAGMENTS) && frag_names;
+    RC_TRY(rt_check_frags(c, d, s, loads, frag, vfrag ? frag_names : nullptr, have, fst));
+    // 3 + 4. one restore launch; the restored segments against their names, their tree against the fid
     const bool vseg = (flags & DM_RESTORE_VERIFY_SEGMENTS) && seg_names, vfid = (flags & DM_RESTORE_VERIFY_FID) && fid;
-    bool all = true;
-    if (vseg || vfid) {
-        std::vector<uint64_t> sa(nseg);
-        for (uint64_t t = 0; t < nseg; t++) sa[t] = reinterpret_cast<uint64_t>(d.data.u8() + t * segment);
-        std::vector<uint8_t> segd;
-        RC_TRY(rt_hash(c, d, s, sa, segment, segd));
-        if (vseg)
-            for (uint64_t t = 0; t < nseg; t++)
-                if (std::memcmp(segd.data() + 32 * t, seg_names + 32 * t, 32) != 0) {
-                    sst[t] = kSegMismatch;
-                    all = false;
-                }
-        if (vfid && all) {
-            uint8_t root[32];
-            RC_TRY(rt_fid(c, d, s, segd.data(), nseg, root));
-            if (std::memcmp(root, fid, 32) != 0) all = false;
-        }
+    std::vector<uint8_t> segd;
+    Rebuild res;
+    RC_TRY(rt_rebuild(r, d, s, have, nseg, d.data.u8(), segment, fst, sst, vseg ? seg_names : nullptr, vfid, segd, res));
+    if (res != Rebuild::kDone) return DM_OK;
+    if (vfid) {
+        uint8_t root[32];
+        RC_TRY(rt_fid(c, d, s, segd.data(), nseg, root));
+        if (std::memcmp(root, fid, 32) != 0) return DM_OK;
     }
-    if (!all) return DM_OK;
     const void* obj = d.data.p;
     if (key) {   // 4b. ciphertext -> the joined plaintext pieces, every padding block checked
+        bool all = true;
         uint8_t* plain = work.u8() + plain_off;
         uint8_t* pad_ok = plain + nseg * piece;
         HIP_TRY(launch_aes_decrypt(d, s, *key, d.data.u8(), segment, segment, nseg, plain, piece, pad_ok));
@@ -277,15 +224,9 @@ int restore_buffer(dm_rs* r, Dev& d, const void* const* frags, const uint8_t* fr
 
 std::atomic<uint64_t> g_rt_seq{0};
 
-struct RtLoad {            // one fragment file to bring to the device
-    uint64_t idx;          // window-local t * total + j
-    std::string path;
-    uint8_t* to;
-};
-
 // Fragment files -> pinned slots (parallel preads) -> HBM, slot by slot; synchronises d.copy.
-int rt_load(dm_rs* r, Dev& d, const std::vector<RtLoad>& loads, uint64_t frag, uint64_t slot_cap, FpEvents& ev,
-            uint64_t& next_slot) {
+int rt_load(dm_rs* r, Dev& d, const std::vector<RtLoad>& loads, const std::vector<std::string>& paths, uint64_t frag,
+            uint64_t slot_cap, FpEvents& ev, uint64_t& next_slot) {
     dm_ctx* c = r->c;
     RsLane& L = rs_ln(r, d);
     const uint64_t per = std::max<uint64_t>(1, slot_cap / frag);
@@ -294,51 +235,13 @@ int rt_load(dm_rs* r, Dev& d, const std::vector<RtLoad>& loads, uint64_t frag, u
         const int sl = (int)(next_slot++ % kFpSlots);
         HIP_TRY(hipEventSynchronize(ev.slot[sl]));   // the slot's previous copies have left it
         uint8_t* buf = L.fp_slot[sl].u8();
-        const size_t J = std::min<size_t>(kRtReaders, n);
-        std::vector<std::future<std::string>> jobs;
-        for (size_t j = 0; j < J; j++)
-            jobs.push_back(std::async(std::launch::async, [&, j]() -> std::string {
-                for (size_t i = j; i < n; i += J) {
-                    const std::string& p = loads[g0 + i].path;
-                    const int fd = ::open(p.c_str(), O_RDONLY | O_CLOEXEC);
-                    if (fd < 0) return "open " + p + ": " + go_errno(errno);
-                    uint64_t done = 0;
-                    while (done < frag) {
-                        const ssize_t got = ::pread(fd, buf + i * frag + done, frag - done, (off_t)done);
-                        if (got < 0 && errno == EINTR) continue;
-                        if (got <= 0) {
-                            const std::string e = got < 0 ? go_errno(errno) : std::string("unexpected EOF");
-                            ::close(fd);
-                            return "read " + p + ": " + e;
-                        }
-                        done += (uint64_t)got;
-                    }
-                    ::close(fd);
-                }
-                return std::string();
-            }));
-        std::string err;
-        for (auto& j : jobs) {
-            const std::string e = j.get();
-            if (err.empty()) err = e;
-        }
+        const std::string err = read_files(paths.data() + g0, n, frag, buf, kRtReaders);
         if (!err.empty()) return fail(c, DM_ERR_IO, "%s", err.c_str());
         for (size_t i = 0; i < n; i++)
             HIP_TRY(hipMemcpyAsync(loads[g0 + i].to, buf + i * frag, frag, hipMemcpyHostToDevice, d.copy));
         HIP_TRY(hipEventRecord(ev.slot[sl], d.copy));
     }
     HIP_TRY(hipStreamSynchronize(d.copy));
-    return DM_OK;
-}
-
-int rt_write_all(dm_ctx* c, int fd, const std::string& path, const uint8_t* p, uint64_t len, uint64_t off) {
-    uint64_t done = 0;
-    while (done < len) {
-        const ssize_t w = ::pwrite(fd, p + done, len - done, (off_t)(off + done));
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) return fail(c, DM_ERR_IO, "write %s: %s", path.c_str(), go_errno(w < 0 ? errno : EIO).c_str());
-        done += (uint64_t)w;
-    }
     return DM_OK;
 }
 
@@ -366,23 +269,24 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
     std::vector<uint8_t> segd_all(vfid ? 32 * nseg : 0);
     bool all = true;
     for (uint64_t w0 = 0; w0 < nseg; w0 += win) {
-        const uint64_t ns = std::min(win, nseg - w0), NF = ns * (uint64_t)total;
+        const uint64_t ns = std::min(win, nseg - w0);
         HIP_TRY(hipStreamSynchronize(s));   // the previous window's kernels are done with the object buffer
         HIP_TRY(d.data.ensure(ns * segment + kAlign));
         HIP_TRY(L.work.ensure(ns * lay.pbytes + 16));
-        std::vector<const uint8_t*> dev(NF, nullptr);
-        std::vector<uint8_t> good(NF, 0);
+        RtFrags have(ns * (uint64_t)total, nullptr);
         std::vector<int> cand(ns, 0), ngood(ns, 0);
         uint8_t* wf = fst + w0 * total;
+        const uint8_t* wnames = frag_names + 32 * w0 * total;
         // 1 + 2. per segment the first k fragment files that exist; further ones while a check fails
         for (;;) {
             std::vector<RtLoad> loads;
+            std::vector<std::string> paths;
             for (uint64_t t = 0; t < ns; t++) {
                 int need = k - ngood[t];
                 while (need > 0 && cand[t] < total) {
                     const int j = cand[t]++;
                     const uint64_t i = t * total + j;
-                    const std::string p = dir + "/" + hex32(frag_names + 32 * ((w0 + t) * total + j));
+                    const std::string p = dir + "/" + hex32(wnames + 32 * i);
                     struct stat st {};
                     if (::stat(p.c_str(), &st) != 0) {
                         if (errno == ENOENT || errno == ENOTDIR) continue;   // not downloaded: absent
@@ -392,55 +296,23 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
                         wf[i] = kFragBad;   // not a fragment of this object's shape
                         continue;
                     }
-                    loads.push_back({i, p, lay.frag_ptr(d.data.u8(), L.work.u8(), t, j)});
+                    loads.push_back({i, lay.frag_ptr(d.data.u8(), L.work.u8(), t, j)});
+                    paths.push_back(p);
                     need--;
                 }
             }
             if (loads.empty()) break;
-            RC_TRY(rt_load(r, d, loads, frag, slot_cap, ev, next_slot));
-            std::vector<uint8_t> dig;
-            if (vfrag) {
-                std::vector<uint64_t> addrs(loads.size());
-                for (size_t q = 0; q < loads.size(); q++) addrs[q] = reinterpret_cast<uint64_t>(loads[q].to);
-                RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
-            }
-            for (size_t q = 0; q < loads.size(); q++) {
-                const uint64_t i = loads[q].idx;
-                if (vfrag && std::memcmp(dig.data() + 32 * q, frag_names + 32 * (w0 * total + i), 32) != 0) {
-                    wf[i] = kFragBad;
-                    continue;
-                }
-                good[i] = 1;
-                dev[i] = loads[q].to;
-                ngood[i / total]++;
-            }
+            RC_TRY(rt_load(r, d, loads, paths, frag, slot_cap, ev, next_slot));
+            RC_TRY(rt_check_frags(c, d, s, loads, frag, vfrag ? wnames : nullptr, have, wf));
+            for (const RtLoad& l : loads) ngood[l.idx / total] += have[l.idx] != nullptr;
         }
-        if (!rt_select(k, total, ns, good.data(), wf, sst + w0)) {
-            all = false;   // nothing of this window is rebuilt; later windows still report their fragments
-            continue;
-        }
-        // 3. one restore launch over the window
-        RestoreBatch b;
-        std::vector<const uint8_t*> use((size_t)total);
-        for (uint64_t t = 0; t < ns; t++) {
-            for (int j = 0; j < total; j++) use[j] = good[t * total + j] ? dev[t * total + j] : nullptr;
-            RC_TRY(restore_add(r, b, use.data(), d.data.u8() + t * segment, frag));
-        }
-        RC_TRY(restore_launch(r, d, s, b, frag / 16));
-        // 4. segment names
-        if (vseg || vfid) {
-            std::vector<uint64_t> sa(ns);
-            for (uint64_t t = 0; t < ns; t++) sa[t] = reinterpret_cast<uint64_t>(d.data.u8() + t * segment);
-            std::vector<uint8_t> segd;
-            RC_TRY(rt_hash(c, d, s, sa, segment, segd));
-            if (vseg)
-                for (uint64_t t = 0; t < ns; t++)
-                    if (std::memcmp(segd.data() + 32 * t, seg_names + 32 * (w0 + t), 32) != 0) {
-                        sst[w0 + t] = kSegMismatch;
-                        all = false;
-                    }
-            if (vfid) std::memcpy(segd_all.data() + 32 * w0, segd.data(), 32 * ns);
-        }
+        // 3 + 4. one restore launch over the window, its segments against their names
+        std::vector<uint8_t> segd;
+        Rebuild res;
+        RC_TRY(rt_rebuild(r, d, s, have, ns, d.data.u8(), segment, wf, sst + w0, vseg ? seg_names + 32 * w0 : nullptr, vfid,
+                          segd, res));
+        if (res != Rebuild::kDone) all = false;   // later windows still report their fragments
+        else if (vfid) std::memcpy(segd_all.data() + 32 * w0, segd.data(), 32 * ns);
         if (!all) continue;
         // 5. the window's bytes through the pinned slots into the output file, cut at the file size
         const uint64_t wbeg = w0 * segment, wend = std::min(size, (w0 + ns) * segment);
@@ -450,7 +322,8 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
             HIP_TRY(hipEventSynchronize(ev.slot[sl]));
             HIP_TRY(hipMemcpyAsync(L.fp_slot[sl].p, d.data.u8() + (o - wbeg), n, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
-            RC_TRY(rt_write_all(c, out_fd, out_name, L.fp_slot[sl].u8(), n, o));
+            const std::string err = pwrite_all(out_fd, out_name, L.fp_slot[sl].u8(), n, o);
+            if (!err.empty()) return fail(c, DM_ERR_IO, "%s", err.c_str());
         }
     }
     if (all && vfid) {
@@ -460,6 +333,27 @@ int retrieve_windows(dm_rs* r, Dev& d, const std::string& dir, const uint8_t* fr
     }
     *ok = all ? 1 : 0;
     return DM_OK;
+}
+
+// dm_restore_buffer and, with `key` (storage for the parsed cipher), dm_restore_cipher_buffer.
+int restore_buffer_call(dm_rs* r, const char* fn, const void* const* frags, const uint8_t* frag_names,
+                        const uint8_t* seg_names, const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment,
+                        int flags, CipherKey* key, const void* cipher, uint64_t cipher_len, void* out,
+                        uint8_t* frag_status, uint8_t* seg_status, int* ok) {
+    if (!r || !ok) return bad_arg();
+    *ok = 0;
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    if (!frags || !out) return fail(c, DM_ERR_INVALID, "%s: null argument", fn);
+    RC_TRY(restore_check(r, nseg, size, segment, key, cipher, cipher_len));
+    RtStatus st(r, nseg);
+    const int rc = restore_buffer(r, c->devs[g], frags, frag_names, seg_names, fid, nseg, size, segment, flags, out,
+                                  st.fst.data(), st.sst.data(), ok, key);
+    // no copy from the caller's memory stays queued, whichever way the call ends
+    if (rc != DM_OK || !*ok) (void)hipStreamSynchronize(c->devs[g].stream);
+    st.copy_out(frag_status, seg_status);
+    return rc;
 }
 
 std::mutex g_plan_mu;
@@ -484,7 +378,7 @@ int dm_rs_restore_plan(int data, int parity, const uint8_t* present, const uint8
         mat = cached;
     }
     RestorePlan p;
-    RC_TRY(restore_plan(nullptr, mat.data(), data, parity, present, in_place, p));
+    RC_TRY(plan_status(nullptr, restore_plan(mat.data(), data, parity, present, in_place, p), data));
     std::memcpy(inputs, p.inputs, sizeof(int) * (size_t)data);
     std::memcpy(outputs, p.outputs, sizeof(int) * (size_t)p.nout);
     std::memcpy(rows, p.rows, (size_t)p.nout * (size_t)data);
@@ -508,11 +402,11 @@ int dm_rs_restore_device_async(dm_rs* r, const void* const* dev_frags, uint64_t 
             return fail(c, DM_ERR_INVALID, "dm_rs_restore_device_async: fragment %llu of segment %llu not 16-byte aligned",
                         (unsigned long long)(i % total), (unsigned long long)(i / total));
     const uint64_t frag = segment / (uint64_t)k;
-    RestoreBatch b;   // every plan first: a segment with too few fragments fails the call before any launch
+    RestoreBatch b{r->mat.data(), k, r->m};   // every plan first: a segment with too few fragments fails the call before any launch
     b.desc.reserve(nseg);
     for (uint64_t t = 0; t < nseg; t++)
-        RC_TRY(restore_add(r, b, reinterpret_cast<const uint8_t* const*>(dev_frags) + t * total,
-                           static_cast<uint8_t*>(dev_obj) + t * segment, frag));
+        RC_TRY(plan_status(c, restore_add(b, reinterpret_cast<const uint8_t* const*>(dev_frags) + t * total,
+                                          static_cast<uint8_t*>(dev_obj) + t * segment, frag), k));
     Dev& d = c->devs[g];
     hipStream_t s = pick_stream(d, stream);
     RC_TRY(begin_call(c, d, s));
@@ -522,52 +416,17 @@ int dm_rs_restore_device_async(dm_rs* r, const void* const* dev_frags, uint64_t 
 int dm_restore_buffer(dm_rs* r, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
                       const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags, void* out,
                       uint8_t* frag_status, uint8_t* seg_status, int* ok) {
-    if (!r || !ok) return bad_arg();
-    *ok = 0;
-    dm_ctx* c = r->c;
-    const int g = rs_lane(c);
-    CallLock lk(c, g, kReserved);
-    if (!frags || !out) return fail(c, DM_ERR_INVALID, "dm_restore_buffer: null argument");
-    RC_TRY(restore_check(r, nseg, size, segment));
-    std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
-    const int rc = restore_buffer(r, c->devs[g], frags, frag_names, seg_names, fid, nseg, size, segment, flags, out,
-                                  fst.data(), sst.data(), ok);
-    // no copy from the caller's memory stays queued, whichever way the call ends
-    if (rc != DM_OK || !*ok) (void)hipStreamSynchronize(c->devs[g].stream);
-    if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
-    if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
-    return rc;
+    return restore_buffer_call(r, "dm_restore_buffer", frags, frag_names, seg_names, fid, nseg, size, segment, flags,
+                               nullptr, nullptr, 0, out, frag_status, seg_status, ok);
 }
 
 int dm_restore_cipher_buffer(dm_rs* r, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
                              const uint8_t* fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
                              const void* cipher, uint64_t cipher_len, void* out, uint8_t* frag_status,
                              uint8_t* seg_status, int* ok) {
-    if (!r || !ok) return bad_arg();
-    *ok = 0;
-    dm_ctx* c = r->c;
-    const int g = rs_lane(c);
-    CallLock lk(c, g, kReserved);
-    if (!frags || !out) return fail(c, DM_ERR_INVALID, "dm_restore_cipher_buffer: null argument");
-    if (nseg == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
-    RC_TRY(process_check(r, size ? size : 1, segment));
-    if (!dm_cipher::segment_ok(segment))
-        return fail(c, DM_ERR_INVALID, "segment size %llu has no room for a block and its padding block",
-                    (unsigned long long)segment);
     CipherKey key;
-    RC_TRY(cipher_key(c, cipher, cipher_len, key));
-    if (!dm_cipher::size_ok(size, nseg, segment))
-        return fail(c, DM_ERR_INVALID, "size %llu does not end in the last of %llu pieces of %llu bytes",
-                    (unsigned long long)size, (unsigned long long)nseg,
-                    (unsigned long long)(segment - dm_cipher::kBlock));
-    std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
-    const int rc = restore_buffer(r, c->devs[g], frags, frag_names, seg_names, fid, nseg, size, segment, flags, out,
-                                  fst.data(), sst.data(), ok, &key);
-    // no copy from the caller's memory stays queued, whichever way the call ends
-    if (rc != DM_OK || !*ok) (void)hipStreamSynchronize(c->devs[g].stream);
-    if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
-    if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
-    return rc;
+    return restore_buffer_call(r, "dm_restore_cipher_buffer", frags, frag_names, seg_names, fid, nseg, size, segment,
+                               flags, &key, cipher, cipher_len, out, frag_status, seg_status, ok);
 }
 
 int dm_retrieve_file(dm_rs* r, const char* fragdir, const uint8_t* frag_names, const uint8_t* seg_names,
@@ -591,9 +450,9 @@ int dm_retrieve_file(dm_rs* r, const char* fragdir, const uint8_t* frag_names, c
     fd.fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (fd.fd < 0) return fail(c, DM_ERR_IO, "open %s: %s", outp.c_str(), go_errno(errno).c_str());   // as os.Create(out_path)
     Dev& d = c->devs[g];
-    std::vector<uint8_t> fst(nseg * (uint64_t)(r->k + r->m), 0), sst(nseg, 0);
-    int rc = retrieve_windows(r, d, dir, frag_names, seg_names, fid, nseg, size, segment, flags, fd.fd, tmp, fst.data(),
-                              sst.data(), ok);
+    RtStatus st(r, nseg);
+    int rc = retrieve_windows(r, d, dir, frag_names, seg_names, fid, nseg, size, segment, flags, fd.fd, tmp,
+                              st.fst.data(), st.sst.data(), ok);
     if (rc != DM_OK) {   // a failed call may leave copies queued: none may land in a slot the next call fills
         (void)hipStreamSynchronize(d.copy);
         (void)hipStreamSynchronize(d.stream);
@@ -608,8 +467,7 @@ int dm_retrieve_file(dm_rs* r, const char* fragdir, const uint8_t* frag_names, c
         if (rc != DM_OK) *ok = 0;
     }
     if (rc != DM_OK || !*ok) ::unlink(tmp.c_str());   // no temporary survives a failed call
-    if (frag_status) std::memcpy(frag_status, fst.data(), fst.size());
-    if (seg_status) std::memcpy(seg_status, sst.data(), sst.size());
+    st.copy_out(frag_status, seg_status);
     return rc;
 }
 

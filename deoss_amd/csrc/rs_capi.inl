@@ -8,97 +8,11 @@
 //   Reconstruct(shards)    -> dm_rs_reconstruct / dm_rs_reconstruct_device_async
 //   Verify(shards)         -> dm_rs_verify
 //   Split + Encode of one segment -> dm_rs_encode_buffer
-// The GF(2^8) arithmetic below only builds the small coding tables; all shard bytes are coded
+// The GF(2^8) arithmetic (rs_plan.hpp) only builds the small coding tables; all shard bytes are coded
 // by rs_code_kernel on the GPU (no CPU fallback).
-#include "rs_kernels.hpp"
+#include "rs_kernels.hpp"   // includes rs_plan.hpp: the host side of the coding (matrices, tables, plans)
 
-namespace {
-
-struct Gf {
-    uint8_t exp[510];
-    uint8_t log[256];
-    Gf() {
-        unsigned x = 1;
-        for (int i = 0; i < 255; i++) {
-            exp[i] = (uint8_t)x;
-            log[x] = (uint8_t)i;
-            x <<= 1;
-            if (x & 0x100) x ^= 0x11d;   // x^8 + x^4 + x^3 + x^2 + 1 (klauspost "29")
-        }
-        for (int i = 255; i < 510; i++) exp[i] = exp[i - 255];
-        log[0] = 0;
-    }
-    uint8_t mul(uint8_t a, uint8_t b) const { return (a && b) ? exp[log[a] + log[b]] : 0; }
-    uint8_t inv(uint8_t a) const { return exp[255 - log[a]]; }
-    uint8_t pow(uint8_t a, int n) const { return n == 0 ? 1 : (a == 0 ? 0 : exp[(log[a] * n) % 255]); }
-};
-
-const Gf& gf() {
-    static const Gf g;
-    return g;
-}
-
-// Gauss-Jordan inverse of a k x k GF(2^8) matrix; false if singular.
-bool gf_invert(const uint8_t* m, int k, uint8_t* out) {
-    const Gf& g = gf();
-    uint8_t w[dm::kRsMaxIn][2 * dm::kRsMaxIn];
-    for (int r = 0; r < k; r++)
-        for (int c = 0; c < k; c++) {
-            w[r][c] = m[r * k + c];
-            w[r][k + c] = (uint8_t)(r == c);
-        }
-    for (int c = 0; c < k; c++) {
-        int p = c;
-        while (p < k && w[p][c] == 0) p++;
-        if (p == k) return false;
-        if (p != c)
-            for (int j = 0; j < 2 * k; j++) std::swap(w[p][j], w[c][j]);
-        const uint8_t s = g.inv(w[c][c]);
-        for (int j = 0; j < 2 * k; j++) w[c][j] = g.mul(w[c][j], s);
-        for (int r = 0; r < k; r++) {
-            if (r == c || w[r][c] == 0) continue;
-            const uint8_t f = w[r][c];
-            for (int j = 0; j < 2 * k; j++) w[r][j] ^= g.mul(f, w[c][j]);
-        }
-    }
-    for (int r = 0; r < k; r++)
-        for (int c = 0; c < k; c++) out[r * k + c] = w[r][k + c];
-    return true;
-}
-
-// klauspost buildMatrix: vandermonde(total, k) x inverse(top k x k), (k + m) x k row-major.
-bool rs_build_matrix(int k, int m, std::vector<uint8_t>& mat) {
-    const Gf& g = gf();
-    const int total = k + m;
-    std::vector<uint8_t> vm((size_t)total * k);
-    for (int i = 0; i < total; i++)
-        for (int j = 0; j < k; j++) vm[(size_t)i * k + j] = g.pow((uint8_t)i, j);
-    uint8_t inv[dm::kRsMaxIn * dm::kRsMaxIn];
-    if (!gf_invert(vm.data(), k, inv)) return false;
-    mat.assign((size_t)total * k, 0);
-    for (int i = 0; i < total; i++)
-        for (int j = 0; j < k; j++) {
-            uint8_t acc = 0;
-            for (int t = 0; t < k; t++) acc ^= g.mul(vm[(size_t)i * k + t], inv[t * k + j]);
-            mat[(size_t)i * k + j] = acc;
-        }
-    return true;
-}
-
-// Lookup table of `rows` (nout x k, row-major): entry [j][x] byte i = rows[i][j] * x.
-std::vector<uint64_t> rs_table(const uint8_t* rows, int nout, int k) {
-    const Gf& g = gf();
-    std::vector<uint64_t> t((size_t)k * 256, 0);
-    for (int j = 0; j < k; j++)
-        for (int x = 0; x < 256; x++) {
-            uint64_t e = 0;
-            for (int i = 0; i < nout; i++) e |= (uint64_t)g.mul(rows[i * k + j], (uint8_t)x) << (8 * i);
-            t[(size_t)j * 256 + x] = e;
-        }
-    return t;
-}
-
-}  // namespace
+using namespace dm_rsplan;
 
 namespace {
 
@@ -183,25 +97,23 @@ dm::RsArgs rs_encode_args(const dm_rs* r, const uint8_t* data, uint64_t data_str
     return a;
 }
 
+// What rs_pick_inputs and the plans built on it return (rs_plan.hpp), as the call's error.
+int plan_status(dm_ctx* c, int got, int k) {
+    if (got == k) return DM_OK;
+    if (got == kPlanSingular) return fail(c, DM_ERR_INVALID, "singular decode matrix");
+    return fail(c, DM_ERR_INVALID, "too few shards given (%d of %d needed)", got, k);
+}
+
 // Coding rows that rebuild the missing shards from the first k present ones (klauspost
 // Reconstruct: the first `data` valid shards in index order; missing data rows come from the
 // inverse of their sub-matrix, missing parity rows = parity row x that inverse).
 int rs_decode_plan(dm_rs* r, const uint8_t* present, int* valid, int* missing, int* nmiss, std::vector<uint8_t>& rows) {
-    dm_ctx* c = r->c;
     const int k = r->k, total = r->k + r->m;
-    int nv = 0;
     *nmiss = 0;
-    for (int i = 0; i < total; i++) {
-        if (present[i]) {
-            if (nv < k) valid[nv++] = i;
-        } else {
-            missing[(*nmiss)++] = i;
-        }
-    }
-    if (nv < k) return fail(c, DM_ERR_INVALID, "too few shards given (%d of %d needed)", nv, k);
-    uint8_t sub[dm::kRsMaxIn * dm::kRsMaxIn], inv[dm::kRsMaxIn * dm::kRsMaxIn];
-    for (int i = 0; i < k; i++) std::memcpy(sub + i * k, r->mat.data() + valid[i] * k, (size_t)k);
-    if (!gf_invert(sub, k, inv)) return fail(c, DM_ERR_INVALID, "singular decode matrix");
+    for (int i = 0; i < total; i++)
+        if (!present[i]) missing[(*nmiss)++] = i;
+    uint8_t inv[dm::kRsMaxIn * dm::kRsMaxIn];
+    RC_TRY(plan_status(r->c, rs_pick_inputs(r->mat.data(), k, r->m, present, valid, inv), k));
     const Gf& g = gf();
     rows.assign((size_t)*nmiss * k, 0);
     for (int t = 0; t < *nmiss; t++) {
@@ -407,7 +319,7 @@ int dm_rs_reconstruct(dm_rs* r, void* const* shards, const uint8_t* present, uin
     int nv = 0;
     for (int i = 0; i < total; i++) nv += present[i] != 0;
     if (nv == total) return DM_OK;
-    if (nv < r->k) return fail(c, DM_ERR_INVALID, "too few shards given (%d of %d needed)", nv, r->k);
+    if (nv < r->k) return plan_status(c, nv, r->k);
     Dev& d = c->devs[g];
     DevBuf& work = rs_ln(r, d).work;
     hipStream_t s = d.stream;

@@ -22,10 +22,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rs_plan.hpp"   // kRsMaxIn, kRsMaxOut, RsRestoreDesc (built on the host)
+
 namespace dm {
 
-constexpr int kRsMaxIn = 8;
-constexpr int kRsMaxOut = 8;
 constexpr int kRsThreads = 256;
 
 struct RsArgs {
@@ -149,17 +149,7 @@ void rs_code_kernel(RsArgs a) {
 
 // ---- restore: many segments, each with its own erasure pattern, in one launch -----------------
 // The download side (cess-go-sdk process.Retrievefile: erasure.RSRestore per segment, join,
-// truncate).  Segment s has a descriptor: the k fragments it is rebuilt from, the data fragments
-// that are not yet at their final address in the object, and which coding table maps one to the
-// other (a missing fragment's row comes from the inverse sub-matrix, a fragment that is present
-// but lies elsewhere has a unit row: gather and decode are one pass).
-struct RsRestoreDesc {
-    const uint8_t* in[kRsMaxIn];   // the first k usable fragments, in index order
-    uint8_t* out[kRsMaxIn];        // final addresses of the data fragments to write (nout <= k)
-    uint32_t nout;                 // 0: every data fragment is in place, nothing to do
-    uint32_t table;                // index into RsRestoreArgs::tables
-};
-
+// truncate).  Segment s has a descriptor (RsRestoreDesc, rs_plan.hpp).
 struct RsRestoreArgs {
     const RsRestoreDesc* desc;     // [nseg]
     const uint2* tables;           // [ntab][k][256] x 8 B, rs_code_kernel's layout

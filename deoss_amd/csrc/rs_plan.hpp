@@ -1,0 +1,248 @@
+// rs_plan.hpp -- what the Reed-Solomon entry points decide before a launch (pure host code, no
+// HIP): the GF(2^8) arithmetic behind the coding tables, a reconstruction's inputs and rows, a
+// restore's statuses, and the descriptors and tables of one restore launch.
+//
+// Shared by rs_capi.inl, restore_capi.inl, rs_kernels.hpp (the shard limits and the descriptor its
+// kernel reads) and the host test (tests/cpp/test_rs_plan.cpp, plain and ASan/UBSan, no GPU).
+// Mirrors klauspost/reedsolomon v1.12.4: its default matrix, and Reconstruct's choice of inputs.
+#pragma once
+
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace dm {
+
+constexpr int kRsMaxIn = 8;
+constexpr int kRsMaxOut = 8;
+
+// One restored segment: the fragments to read, the data fragments to write -- those not yet at their
+// final address in the object -- and the coding table that maps one to the other (a missing
+// fragment's row comes from the inverse sub-matrix, a present one elsewhere has a unit row).
+struct RsRestoreDesc {
+    const uint8_t* in[kRsMaxIn];   // the first k usable fragments, in index order
+    uint8_t* out[kRsMaxIn];        // final addresses of the data fragments to write (nout <= k)
+    uint32_t nout;                 // 0: every data fragment is in place, nothing to do
+    uint32_t table;                // index into RsRestoreArgs::tables
+};
+
+}  // namespace dm
+
+namespace dm_rsplan {
+
+using dm::kRsMaxIn;
+using dm::kRsMaxOut;
+
+struct Gf {
+    uint8_t exp[510];
+    uint8_t log[256];
+    Gf() {
+        unsigned x = 1;
+        for (int i = 0; i < 255; i++) {
+            exp[i] = (uint8_t)x;
+            log[x] = (uint8_t)i;
+            x <<= 1;
+            if (x & 0x100) x ^= 0x11d;   // x^8 + x^4 + x^3 + x^2 + 1 (klauspost "29")
+        }
+        for (int i = 255; i < 510; i++) exp[i] = exp[i - 255];
+        log[0] = 0;
+    }
+    uint8_t mul(uint8_t a, uint8_t b) const { return (a && b) ? exp[log[a] + log[b]] : 0; }
+    uint8_t inv(uint8_t a) const { return exp[255 - log[a]]; }
+    uint8_t pow(uint8_t a, int n) const { return n == 0 ? 1 : (a == 0 ? 0 : exp[(log[a] * n) % 255]); }
+};
+
+inline const Gf& gf() {
+    static const Gf g;
+    return g;
+}
+
+// Gauss-Jordan inverse of a k x k GF(2^8) matrix; false if singular.
+inline bool gf_invert(const uint8_t* m, int k, uint8_t* out) {
+    const Gf& g = gf();
+    uint8_t w[kRsMaxIn][2 * kRsMaxIn];
+    for (int r = 0; r < k; r++)
+        for (int c = 0; c < k; c++) {
+            w[r][c] = m[r * k + c];
+            w[r][k + c] = (uint8_t)(r == c);
+        }
+    for (int c = 0; c < k; c++) {
+        int p = c;
+        while (p < k && w[p][c] == 0) p++;
+        if (p == k) return false;
+        if (p != c)
+            for (int j = 0; j < 2 * k; j++) std::swap(w[p][j], w[c][j]);
+        const uint8_t s = g.inv(w[c][c]);
+        for (int j = 0; j < 2 * k; j++) w[c][j] = g.mul(w[c][j], s);
+        for (int r = 0; r < k; r++) {
+            if (r == c || w[r][c] == 0) continue;
+            const uint8_t f = w[r][c];
+            for (int j = 0; j < 2 * k; j++) w[r][j] ^= g.mul(f, w[c][j]);
+        }
+    }
+    for (int r = 0; r < k; r++)
+        for (int c = 0; c < k; c++) out[r * k + c] = w[r][k + c];
+    return true;
+}
+
+// klauspost buildMatrix: vandermonde(total, k) x inverse(top k x k), (k + m) x k row-major.
+inline bool rs_build_matrix(int k, int m, std::vector<uint8_t>& mat) {
+    const Gf& g = gf();
+    const int total = k + m;
+    std::vector<uint8_t> vm((size_t)total * k);
+    for (int i = 0; i < total; i++)
+        for (int j = 0; j < k; j++) vm[(size_t)i * k + j] = g.pow((uint8_t)i, j);
+    uint8_t inv[kRsMaxIn * kRsMaxIn];
+    if (!gf_invert(vm.data(), k, inv)) return false;
+    mat.assign((size_t)total * k, 0);
+    for (int i = 0; i < total; i++)
+        for (int j = 0; j < k; j++) {
+            uint8_t acc = 0;
+            for (int t = 0; t < k; t++) acc ^= g.mul(vm[(size_t)i * k + t], inv[t * k + j]);
+            mat[(size_t)i * k + j] = acc;
+        }
+    return true;
+}
+
+// Lookup table of `rows` (nout x k, row-major): entry [j][x] byte i = rows[i][j] * x.
+inline std::vector<uint64_t> rs_table(const uint8_t* rows, int nout, int k) {
+    const Gf& g = gf();
+    std::vector<uint64_t> t((size_t)k * 256, 0);
+    for (int j = 0; j < k; j++)
+        for (int x = 0; x < 256; x++) {
+            uint64_t e = 0;
+            for (int i = 0; i < nout; i++) e |= (uint64_t)g.mul(rows[i * k + j], (uint8_t)x) << (8 * i);
+            t[(size_t)j * 256 + x] = e;
+        }
+    return t;
+}
+
+constexpr int kPlanSingular = -1;
+
+// The inputs of one pattern (klauspost's Reconstruct): the first k present fragments in index order,
+// and the inverse of their rows of the coding matrix `mat` ((k + m) x k).  Returns k; or, without a
+// plan, how many fragments (< k: too few) are present, or kPlanSingular.
+inline int rs_pick_inputs(const uint8_t* mat, int k, int m, const uint8_t* present, int* inputs, uint8_t* inv) {
+    int nv = 0;
+    for (int i = 0; i < k + m && nv < k; i++)
+        if (present[i]) inputs[nv++] = i;
+    if (nv < k) return nv;
+    uint8_t sub[kRsMaxIn * kRsMaxIn] = {};
+    for (int i = 0; i < k; i++) std::memcpy(sub + i * k, mat + inputs[i] * k, (size_t)k);
+    return gf_invert(sub, k, inv) ? k : kPlanSingular;
+}
+
+struct RestorePlan {
+    int inputs[kRsMaxIn];
+    int outputs[kRsMaxIn];
+    int nout = 0;
+    uint8_t rows[kRsMaxIn * kRsMaxIn];   // nout x k
+};
+
+// The plan of one pattern: every data fragment that is missing or not at its final address is
+// written, fragment j with row j of the inverse of the inputs' sub-matrix (a unit row when j is
+// itself an input: a present data fragment always is).  in_place is nullable (nothing in place).
+// Returns as rs_pick_inputs.
+inline int restore_plan(const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* in_place,
+                        RestorePlan& p) {
+    uint8_t inv[kRsMaxIn * kRsMaxIn];
+    const int got = rs_pick_inputs(mat, k, m, present, p.inputs, inv);
+    if (got != k) return got;
+    p.nout = 0;
+    for (int j = 0; j < k; j++) {
+        if (present[j] && in_place && in_place[j]) continue;
+        p.outputs[p.nout] = j;
+        std::memcpy(p.rows + p.nout * k, inv + j * k, (size_t)k);
+        p.nout++;
+    }
+    return k;
+}
+
+enum : uint8_t { kFragAbsent = 0, kFragUsed = 1, kFragSpare = 2, kFragBad = 3 };
+enum : uint8_t { kSegOk = 0, kSegTooFew = 1, kSegMismatch = 2, kSegBadPadding = 3 };
+
+// Fragment states of ns segments -> statuses: the first k good fragments of a segment are used, the
+// other good ones spare; a segment with fewer than k good ones is kSegTooFew (its good fragments
+// stay spare: nothing is rebuilt from them).  `good` holds the address of a fragment that is on the
+// device and passed its check, else null.  Returns false when any segment has too few.
+inline bool rt_select(int k, int total, uint64_t ns, const uint8_t* const* good, uint8_t* fst, uint8_t* sst) {
+    bool all = true;
+    for (uint64_t t = 0; t < ns; t++) {
+        int ng = 0;
+        for (int j = 0; j < total; j++) ng += good[t * total + j] != nullptr;
+        const bool enough = ng >= k;
+        if (!enough) {
+            sst[t] = kSegTooFew;
+            all = false;
+        }
+        int used = 0;
+        for (int j = 0; j < total; j++)
+            if (good[t * total + j]) fst[t * total + j] = (enough && used++ < k) ? kFragUsed : kFragSpare;
+    }
+    return all;
+}
+
+// Descriptors and coding tables of one restore launch, built segment by segment; mat is the coder's
+// (k + m) x k matrix and outlives the batch.
+struct RestoreBatch {
+    struct Cached {
+        RestorePlan p;
+        uint32_t tab;
+    };
+    const uint8_t* mat;
+    int k, m;
+    std::vector<dm::RsRestoreDesc> desc;
+    std::vector<uint64_t> tabs;                 // [ntab][k][256]
+    std::map<uint32_t, Cached> plans;           // present mask | in-place mask << 16
+    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index (one table per distinct plan)
+    bool any_out = false;
+};
+
+// Segment whose usable fragments are frags[0 .. total) (device addresses, NULL = absent; never
+// dereferenced here) and whose data fragment j belongs at seg_base + j * frag.  Returns as
+// rs_pick_inputs.
+inline int restore_add(RestoreBatch& b, const uint8_t* const* frags, uint8_t* seg_base, uint64_t frag) {
+    const int k = b.k, total = b.k + b.m;
+    uint8_t present[kRsMaxIn + kRsMaxOut], in_place[kRsMaxIn];
+    uint32_t key = 0;
+    for (int j = 0; j < total; j++) {
+        present[j] = frags[j] != nullptr;
+        key |= (uint32_t)present[j] << j;
+        if (j < k) {
+            in_place[j] = frags[j] == seg_base + (uint64_t)j * frag;
+            key |= (uint32_t)in_place[j] << (16 + j);
+        }
+    }
+    auto it = b.plans.find(key);
+    if (it == b.plans.end()) {
+        RestoreBatch::Cached cp;
+        const int got = restore_plan(b.mat, k, b.m, present, in_place, cp.p);
+        if (got != k) return got;
+        cp.tab = 0;
+        if (cp.p.nout) {
+            const std::string rows(reinterpret_cast<const char*>(cp.p.rows), (size_t)cp.p.nout * k);
+            auto t = b.tab_of.find(rows);
+            if (t == b.tab_of.end()) {
+                const std::vector<uint64_t> tab = rs_table(cp.p.rows, cp.p.nout, k);
+                t = b.tab_of.emplace(rows, (uint32_t)(b.tabs.size() / ((size_t)k * 256))).first;
+                b.tabs.insert(b.tabs.end(), tab.begin(), tab.end());
+            }
+            cp.tab = t->second;
+        }
+        it = b.plans.emplace(key, cp).first;
+    }
+    const RestorePlan& p = it->second.p;
+    dm::RsRestoreDesc ds{};
+    for (int j = 0; j < k; j++) ds.in[j] = frags[p.inputs[j]];
+    for (int i = 0; i < p.nout; i++) ds.out[i] = seg_base + (uint64_t)p.outputs[i] * frag;
+    ds.nout = (uint32_t)p.nout;
+    ds.table = it->second.tab;
+    if (p.nout) b.any_out = true;
+    b.desc.push_back(ds);
+    return k;
+}
+
+}  // namespace dm_rsplan

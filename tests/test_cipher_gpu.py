@@ -318,6 +318,37 @@ def test_restore_buffer_cipher(ctx, segment, klen):
     p.close()
 
 
+def test_restore_buffer_cipher_with_and_without_a_spare(ctx):
+    """5 of 12 fragments with one used fragment corrupt: the spare takes its place and the plaintext
+    is exact.  4 of 12 with one corrupt: too few, and nothing is written to the caller's buffer."""
+    segment, key, total = 256, KEYS[16], 12
+    fsz, n = segment // 4, 3 * (segment - 16) + 7
+    p = _processor(ctx, segment)
+    buf = _object(n, 4242)
+    seg, fragn, fid, frags = p.process_buffer(buf, want_frags=True, cipher=key)
+    nseg = len(seg) // 32
+    full = [[frags[(s * total + j) * fsz:(s * total + j + 1) * fsz] for j in range(total)] for s in range(nseg)]
+    kept = [[1, 3, 6, 8, 11], [0, 5, 7, 9, 10], [2, 3, 4, 5, 6], [0, 1, 2, 3, 4]]
+    assert nseg == len(kept)
+    have = [[f if j in kept[s] else None for j, f in enumerate(row)] for s, row in enumerate(full)]
+    for s in range(nseg):
+        j = kept[s][s % 4]
+        h = have[s][j]
+        have[s][j] = h[:5] + bytes([h[5] ^ 0x20]) + h[6:]
+    ok, data, fst, sst = p.restore_buffer(have, n, frag_names=fragn, seg_names=seg, fid=fid, cipher=key)
+    assert ok and data == buf and sst == bytes(nseg)
+    for s in range(nseg):
+        want = [3 if j == kept[s][s % 4] else 1 if j in kept[s] else 0 for j in range(total)]
+        assert list(fst[s * total:(s + 1) * total]) == want, s
+    few = [[f if j in kept[s][:4] else None for j, f in enumerate(row)] for s, row in enumerate(full)]
+    few[2][kept[2][1]] = bytes([few[2][kept[2][1]][0] ^ 1]) + few[2][kept[2][1]][1:]
+    out = ctypes.create_string_buffer(bytes([0x5A]) * n, n)
+    ok, data, fst, sst = p.restore_buffer(few, n, frag_names=fragn, seg_names=seg, fid=fid, cipher=key, out=out)
+    assert not ok and data is None and list(sst) == [0, 0, 1, 0]
+    assert out.raw == bytes([0x5A]) * n and fst[2 * total + kept[2][1]] == 3
+    p.close()
+
+
 # ---- the mirrors -----------------------------------------------------------------------------------
 
 MIRROR_CIPHER = "0123456789abcdef0123456789abcdef"

@@ -403,6 +403,84 @@ def test_retrieve_file_segment_without_fragments_leaves_nothing_behind(stored, t
     assert e.value.code == -6 and "no such file or directory" in str(e.value)
 
 
+def _three_windows(monkeypatch):
+    monkeypatch.setenv("DEOSS_RT_WINDOW_BYTES", str(4 * FSEG))   # segments 0-3, 4-7, 8-9
+
+
+def test_retrieve_file_failed_middle_window(stored, tmp_path, monkeypatch):
+    """A segment of the second of three windows has no fragment files: that window is not rebuilt,
+    the windows before and after it still report their fragments, nothing is left behind."""
+    p, buf, segd, fragd, fid, d = stored
+    kept = [2, 4, 7, 11]
+    fd = _fragment_dir(stored, tmp_path, lambda s: [] if s == 5 else kept)
+    outdir = tmp_path / "out"
+    outdir.mkdir()
+    _three_windows(monkeypatch)
+    ok, fst, sst = p.retrieve_file(str(fd), fragd, len(buf), str(outdir / "object"), segd, fid)
+    assert not ok and list(sst) == [1 if s == 5 else 0 for s in range(10)]
+    for s in (0, 1, 2, 3, 8, 9):
+        assert list(fst[12 * s:12 * s + 12]) == [USED if j in kept else ABSENT for j in range(12)], s
+    assert list(fst[60:72]) == [ABSENT] * 12
+    assert os.listdir(outdir) == []
+
+
+def test_retrieve_file_wrong_fid_across_windows(stored, tmp_path, monkeypatch):
+    """Only the fid is checked, over the digests of three windows: one flipped bit fails the call
+    after every window was rebuilt; the right fid gives the object back."""
+    p, buf, segd, fragd, fid, d = stored
+    fd = _fragment_dir(stored, tmp_path, lambda s: [0, 3, 5, 10])
+    outdir = tmp_path / "out"
+    outdir.mkdir()
+    _three_windows(monkeypatch)
+    wrong = fid[:17] + bytes([fid[17] ^ 0x04]) + fid[18:]
+    ok, fst, sst = p.retrieve_file(str(fd), fragd, len(buf), str(outdir / "object"), None, wrong, flags=VID)
+    assert not ok and sst == bytes(10)
+    assert os.listdir(outdir) == []
+    ok, fst, sst = p.retrieve_file(str(fd), fragd, len(buf), str(outdir / "object"), None, fid, flags=VID)
+    assert ok and sst == bytes(10)
+    assert (outdir / "object").read_bytes() == buf
+    assert os.listdir(outdir) == ["object"]
+
+
+def test_retrieve_file_segment_mismatch_in_first_window(stored, tmp_path, monkeypatch):
+    """Segment names only: a corrupt used fragment of segment 1 shows as that segment's mismatch;
+    the later windows still load and report their fragments, and nothing is written."""
+    p, buf, segd, fragd, fid, d = stored
+    kept = [1, 6, 8, 9]
+    fd = _fragment_dir(stored, tmp_path, lambda s: kept)
+    name = fragd[32 * (12 * 1 + 6):32 * (12 * 1 + 7)].hex()
+    (fd / name).write_bytes(_flip((fd / name).read_bytes()))
+    outdir = tmp_path / "out"
+    outdir.mkdir()
+    _three_windows(monkeypatch)
+    ok, fst, sst = p.retrieve_file(str(fd), fragd, len(buf), str(outdir / "object"), segd, None, flags=VS)
+    assert not ok and list(sst) == [2 if s == 1 else 0 for s in range(10)]
+    for s in range(10):
+        assert list(fst[12 * s:12 * s + 12]) == [USED if j in kept else ABSENT for j in range(12)], s
+    assert os.listdir(outdir) == []
+
+
+def test_retrieve_file_candidate_reload_across_slots(stored, tmp_path, monkeypatch):
+    """6 files per segment, the first kept one of two segments corrupt, 3 fragments per pinned slot:
+    the replacements are loaded in a second round through reused slots."""
+    p, buf, segd, fragd, fid, d = stored
+    kept = [1, 2, 4, 7, 9, 10]
+    fd = _fragment_dir(stored, tmp_path, lambda s: kept)
+    for s in (2, 7):
+        name = fragd[32 * (12 * s + 1):32 * (12 * s + 2)].hex()
+        (fd / name).write_bytes(_flip((fd / name).read_bytes(), s))
+    monkeypatch.setenv("DEOSS_FP_SLOT_BYTES", str(3 * (FSEG // 4)))
+    out = tmp_path / "object"
+    ok, fst, sst = p.retrieve_file(str(fd), fragd, len(buf), str(out), segd, fid)
+    assert ok and sst == bytes(10) and out.read_bytes() == buf
+    for s in range(10):
+        if s in (2, 7):   # the fifth kept file takes the corrupt one's place, the sixth is never read
+            want = [0, BAD, USED, 0, USED, 0, 0, USED, 0, USED, 0, 0]
+        else:
+            want = [0, USED, USED, 0, USED, 0, 0, USED, 0, 0, 0, 0]
+        assert list(fst[12 * s:12 * s + 12]) == want, s
+
+
 def test_restore_file_inverts_full_processing(tmp_path):
     """The module-level mirrors at chain sizes: FullProcessing, 8 of 12 fragment files deleted,
     RestoreFile gives the file back."""
