@@ -39,6 +39,7 @@ EXPORTS = (
     "dm_rs_verify", "dm_rs_encode_device_async", "dm_rs_reconstruct_device_async",
     "dm_process_device_async", "dm_process_buffer", "dm_process_batch", "dm_full_processing", "dm_fragment_lookup",
     "dm_rs_restore_plan", "dm_rs_restore_device_async", "dm_restore_buffer", "dm_retrieve_file",
+    "dm_rs_repair_plan", "dm_rs_repair_device_async", "dm_repair_buffer", "dm_repair_files",
     "dm_aes_cbc_encrypt_device_async", "dm_aes_cbc_decrypt_device_async", "dm_process_cipher_buffer",
     "dm_restore_cipher_buffer",
     "dm_pstream_open", "dm_pstream_write", "dm_pstream_close", "dm_pstream_abort",
@@ -119,6 +120,11 @@ def _declare(L: ctypes.CDLL) -> None:
         "dm_restore_buffer": ([vp, pvp, vp, vp, vp, u64, u64, u64, i32, vp, vp, vp, ctypes.POINTER(i32)], i32),
         "dm_retrieve_file": ([vp, ctypes.c_char_p, vp, vp, vp, u64, u64, u64, i32, ctypes.c_char_p, vp, vp,
                               ctypes.POINTER(i32)], i32),
+        "dm_rs_repair_plan": ([i32, i32, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, ctypes.POINTER(i32)],
+                              i32),
+        "dm_rs_repair_device_async": ([vp, pvp, vp, u64, u64, vp], i32),
+        "dm_repair_buffer": ([vp, pvp, pvp, vp, u64, u64, vp, vp, ctypes.POINTER(i32)], i32),
+        "dm_repair_files": ([vp, ctypes.c_char_p, vp, u64, u64, i32, vp, vp, pu64, ctypes.POINTER(i32)], i32),
         "dm_aes_cbc_encrypt_device_async": ([vp, vp, u64, vp, vp, u64, u64, u64, vp], i32),
         "dm_aes_cbc_decrypt_device_async": ([vp, vp, u64, vp, vp, u64, u64, u64, vp, u64, vp, vp], i32),
         "dm_process_cipher_buffer": ([vp, vp, u64, u64, vp, u64, vp, vp, vp, vp], i32),

@@ -21,7 +21,7 @@ namespace {
 struct RsLane {
     DevBuf dec_tab;             // per reconstruct call
     DevBuf work;                // host-API shard staging, process parity, FullProcessing windows
-    DevBuf rst_desc, rst_tab;   // restore: per-segment descriptors, coding tables (restore_capi.inl)
+    DevBuf rst_desc, rst_tab;   // restore, repair: per-segment descriptors, coding tables (restore_capi.inl, repair_capi.inl)
     PinnedBuf fp_slot[4];       // dm_full_processing: file / parity slots (fullproc_capi.inl)
 };
 

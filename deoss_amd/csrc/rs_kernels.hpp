@@ -237,4 +237,94 @@ void rs_restore_kernel(RsRestoreArgs a) {
     }
 }
 
+// ---- repair: the missing fragments of many segments, data or parity, in one launch -------------
+// The storage side (DeOSS node/tracker.go checkFileState): a segment's lost fragments come back
+// from any k survivors.  rs_restore_kernel's descriptors, tables and loop, but a segment may have
+// up to kRsMaxOut outputs whatever NIN is: with HI the high half of the table entry (outputs 4..7)
+// is accumulated and transposed too.  One segment's units; the caller holds its table in LDS.
+template <int NIN, bool HI>
+__device__ __forceinline__ void rs_repair_segment(const uint2* tab, const RsRestoreDesc* ds, uint32_t nout,
+                                                  uint64_t units, uint64_t ustride) {
+    const uint8_t* in[NIN];
+#pragma unroll
+    for (int j = 0; j < NIN; j++) in[j] = ds->in[j];
+    uint8_t* out[HI ? 8 : 4];   // entries past nout are never used
+#pragma unroll
+    for (int i = 0; i < (HI ? 8 : 4); i++) out[i] = ds->out[i];
+    uint64_t u = (uint64_t)blockIdx.x * kRsThreads + threadIdx.x;
+    // register double buffer: the next unit's loads are in flight while this one is coded
+    uint4 nx[NIN];
+    if (u < units) {
+#pragma unroll
+        for (int j = 0; j < NIN; j++) nx[j] = rs_load(in[j] + u * 16);
+    }
+    for (; u < units; u += ustride) {
+        const uint64_t off = u * 16;
+        uint4 x[NIN];
+#pragma unroll
+        for (int j = 0; j < NIN; j++) x[j] = nx[j];
+        if (u + ustride < units) {
+#pragma unroll
+            for (int j = 0; j < NIN; j++) nx[j] = rs_load(in[j] + off + ustride * 16);
+        }
+        uint2 acc[16];
+#pragma unroll
+        for (int p = 0; p < 16; p++) acc[p] = make_uint2(0, 0);
+#pragma unroll
+        for (int j = 0; j < NIN; j++) {
+            const uint32_t w[4] = {x[j].x, x[j].y, x[j].z, x[j].w};
+            const uint2* tj = tab + j * 256;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint2 e = tj[(w[q] >> (8 * k)) & 0xffu];
+                    acc[4 * q + k].x ^= e.x;
+                    if (HI) acc[4 * q + k].y ^= e.y;
+                }
+            }
+        }
+        uint32_t lo[4][4], hi[4][4];   // [q][row]
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            transpose4(acc[4 * q].x, acc[4 * q + 1].x, acc[4 * q + 2].x, acc[4 * q + 3].x, lo[q]);
+            if (HI) transpose4(acc[4 * q].y, acc[4 * q + 1].y, acc[4 * q + 2].y, acc[4 * q + 3].y, hi[q]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (i < (int)nout) rs_store(out[i] + off, make_uint4(lo[0][i], lo[1][i], lo[2][i], lo[3][i]));
+        if (HI) {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i + 4 < (int)nout)
+                    rs_store(out[i + 4] + off, make_uint4(hi[0][i], hi[1][i], hi[2][i], hi[3][i]));
+        }
+    }
+}
+
+// nout, like the table index, depends on seg alone: every wave of the workgroup takes the same
+// side of both branches, whatever mix of widths the workgroup walks.
+template <int NIN>
+__global__ __launch_bounds__(kRsThreads)
+void rs_repair_kernel(RsRestoreArgs a) {
+    __shared__ uint2 tab[NIN * 256];
+    uint32_t cur = 0xffffffffu;
+    const uint64_t ustride = (uint64_t)gridDim.x * kRsThreads;
+    for (uint64_t seg = blockIdx.y; seg < a.nseg; seg += gridDim.y) {
+        const RsRestoreDesc* ds = a.desc + seg;
+        const uint32_t nout = ds->nout;
+        if (nout == 0) continue;
+        const uint32_t ti = ds->table;
+        if (ti != cur) {
+            __syncthreads();   // every wave is done with the previous table
+            const uint2* src = a.tables + (uint64_t)ti * (NIN * 256);
+            for (uint32_t t = threadIdx.x; t < NIN * 256; t += kRsThreads) tab[t] = src[t];
+            __syncthreads();
+            cur = ti;
+        }
+        if (nout > 4) rs_repair_segment<NIN, true>(tab, ds, nout, a.units_per_seg, ustride);
+        else rs_repair_segment<NIN, false>(tab, ds, nout, a.units_per_seg, ustride);
+    }
+}
+
 }  // namespace dm

@@ -1,9 +1,10 @@
 // rs_plan.hpp -- what the Reed-Solomon entry points decide before a launch (pure host code, no
 // HIP): the GF(2^8) arithmetic behind the coding tables, a reconstruction's inputs and rows, a
-// restore's statuses, and the descriptors and tables of one restore launch.
+// restore's statuses, and the descriptors and tables of one restore or one repair launch.
 //
-// Shared by rs_capi.inl, restore_capi.inl, rs_kernels.hpp (the shard limits and the descriptor its
-// kernel reads) and the host test (tests/cpp/test_rs_plan.cpp, plain and ASan/UBSan, no GPU).
+// Shared by rs_capi.inl, restore_capi.inl, repair_capi.inl, rs_kernels.hpp (the shard limits and the
+// descriptor its kernels read) and the host tests (tests/cpp/test_rs_plan.cpp and
+// tests/cpp/test_repair_plan.cpp, plain and ASan/UBSan, no GPU).
 // Mirrors klauspost/reedsolomon v1.12.4: its default matrix, and Reconstruct's choice of inputs.
 #pragma once
 
@@ -21,10 +22,11 @@ constexpr int kRsMaxOut = 8;
 
 // One restored segment: the fragments to read, the data fragments to write -- those not yet at their
 // final address in the object -- and the coding table that maps one to the other (a missing
-// fragment's row comes from the inverse sub-matrix, a present one elsewhere has a unit row).
+// fragment's row comes from the inverse sub-matrix, a present one elsewhere has a unit row).  A
+// repaired segment uses the same descriptor: out holds its missing fragments, data or parity.
 struct RsRestoreDesc {
     const uint8_t* in[kRsMaxIn];   // the first k usable fragments, in index order
-    uint8_t* out[kRsMaxIn];        // final addresses of the data fragments to write (nout <= k)
+    uint8_t* out[kRsMaxIn];        // addresses of the fragments to write (restore: nout <= k; repair: <= kRsMaxOut)
     uint32_t nout;                 // 0: every data fragment is in place, nothing to do
     uint32_t table;                // index into RsRestoreArgs::tables
 };
@@ -241,6 +243,104 @@ inline int restore_add(RestoreBatch& b, const uint8_t* const* frags, uint8_t* se
     ds.nout = (uint32_t)p.nout;
     ds.table = it->second.tab;
     if (p.nout) b.any_out = true;
+    b.desc.push_back(ds);
+    return k;
+}
+
+// ---- repair: the missing fragments of a segment, data or parity, from the survivors -------------
+
+static_assert(kRsMaxOut <= kRsMaxIn, "RsRestoreDesc::out holds a repair's outputs");
+
+struct RepairPlan {
+    int inputs[kRsMaxIn];
+    int outputs[kRsMaxOut];
+    int nout = 0;
+    uint8_t rows[kRsMaxOut * kRsMaxIn];   // nout x k
+};
+
+// The plan of one pattern: every fragment j with want[j] && !present[j] is written (want nullable:
+// every missing one), a data fragment with row j of the inverse of the inputs' sub-matrix, a parity
+// fragment with mat[j] x that inverse.  At most m <= kRsMaxOut fragments are missing once k are
+// present.  Returns as rs_pick_inputs.
+inline int repair_plan(const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* want, RepairPlan& p) {
+    uint8_t inv[kRsMaxIn * kRsMaxIn];
+    const int got = rs_pick_inputs(mat, k, m, present, p.inputs, inv);
+    if (got != k) return got;
+    const Gf& g = gf();
+    p.nout = 0;
+    for (int j = 0; j < k + m; j++) {
+        if (present[j] || (want && !want[j])) continue;
+        uint8_t* row = p.rows + p.nout * k;
+        if (j < k) {
+            std::memcpy(row, inv + j * k, (size_t)k);
+        } else {
+            const uint8_t* mrow = mat + j * k;   // output = mrow x data = mrow x inv x inputs
+            for (int c = 0; c < k; c++) {
+                uint8_t acc = 0;
+                for (int q = 0; q < k; q++) acc ^= g.mul(mrow[q], inv[q * k + c]);
+                row[c] = acc;
+            }
+        }
+        p.outputs[p.nout++] = j;
+    }
+    return k;
+}
+
+// Descriptors and coding tables of one repair launch, built segment by segment (RestoreBatch's
+// counterpart; the descriptor and the table layout are the restore kernel's).
+struct RepairBatch {
+    struct Cached {
+        RepairPlan p;
+        uint32_t tab;
+    };
+    const uint8_t* mat;
+    int k, m;
+    std::vector<dm::RsRestoreDesc> desc;
+    std::vector<uint64_t> tabs;                 // [ntab][k][256]
+    std::map<uint32_t, Cached> plans;           // present mask | want mask << 16
+    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index
+    bool any_out = false;
+    bool any_wide = false;                      // some segment has nout > k: the restore kernel cannot run it
+};
+
+// Segment whose fragment j lies, or is to be written, at frags[j] (device addresses, never
+// dereferenced here): present[j] != 0 holds the fragment; present[j] == 0 and frags[j] != NULL is
+// wanted; NULL is absent and not wanted.  Returns as rs_pick_inputs.
+inline int repair_add(RepairBatch& b, uint8_t* const* frags, const uint8_t* present) {
+    const int k = b.k, total = b.k + b.m;
+    uint8_t pres[kRsMaxIn + kRsMaxOut], want[kRsMaxIn + kRsMaxOut];
+    uint32_t key = 0;
+    for (int j = 0; j < total; j++) {
+        pres[j] = present[j] != 0 && frags[j] != nullptr;
+        want[j] = !pres[j] && frags[j] != nullptr;
+        key |= (uint32_t)pres[j] << j | (uint32_t)want[j] << (16 + j);
+    }
+    auto it = b.plans.find(key);
+    if (it == b.plans.end()) {
+        RepairBatch::Cached cp;
+        const int got = repair_plan(b.mat, k, b.m, pres, want, cp.p);
+        if (got != k) return got;
+        cp.tab = 0;
+        if (cp.p.nout) {
+            const std::string rows(reinterpret_cast<const char*>(cp.p.rows), (size_t)cp.p.nout * k);
+            auto t = b.tab_of.find(rows);
+            if (t == b.tab_of.end()) {
+                const std::vector<uint64_t> tab = rs_table(cp.p.rows, cp.p.nout, k);
+                t = b.tab_of.emplace(rows, (uint32_t)(b.tabs.size() / ((size_t)k * 256))).first;
+                b.tabs.insert(b.tabs.end(), tab.begin(), tab.end());
+            }
+            cp.tab = t->second;
+        }
+        it = b.plans.emplace(key, cp).first;
+    }
+    const RepairPlan& p = it->second.p;
+    dm::RsRestoreDesc ds{};
+    for (int j = 0; j < k; j++) ds.in[j] = frags[p.inputs[j]];
+    for (int i = 0; i < p.nout; i++) ds.out[i] = frags[p.outputs[i]];
+    ds.nout = (uint32_t)p.nout;
+    ds.table = it->second.tab;
+    if (p.nout) b.any_out = true;
+    if (p.nout > k) b.any_wide = true;
     b.desc.push_back(ds);
     return k;
 }

@@ -39,7 +39,9 @@ from .reedsolomon import DATA_SHARDS, PAR_SHARDS, Encoder
 SEGMENT_SIZE = 32 << 20                       # chain.SegmentSize
 FRAGMENT_SIZE = SEGMENT_SIZE // DATA_SHARDS   # chain.FragmentSize (8 MiB; node/tracker.go:250 "96M")
 RESTORE_VERIFY_FRAGMENTS, RESTORE_VERIFY_SEGMENTS, RESTORE_VERIFY_FID, RESTORE_VERIFY_ALL = 1, 2, 4, 7   # DM_RESTORE_*
-CIPHER_BLOCK = 16                             # a piece of segment - 16 plaintext bytes + its PKCS#7 block = one segment
+REPAIR_SCRUB = 1                              # DM_REPAIR_SCRUB
+FRAG_REBUILT = 4                              # frag_status of the repair calls: rebuilt, verified and delivered
+CIPHER_BLOCK = 16                           # a piece of segment - 16 plaintext bytes + its PKCS#7 block = one segment
 SEG_BAD_PADDING = 3                           # seg_status of dm_restore_cipher_buffer: what a wrong cipher looks like
 WINDOW_SEGMENTS = 8                           # segments per GPU call (256 MiB of file + 768 MiB of fragments; the Go shim bounds the segments in flight by DEOSS_PROCESS_MEM_GIB)
 
@@ -317,6 +319,87 @@ class Processor:
                                            "from verified fragments" % ", ".join(map(str, bad)))
         return True, None
 
+    # -- repair (the storage side) -------------------------------------------------------------------
+    def repair_buffer(self, frags, frag_names: bytes, want=None, out=None
+                      ) -> Tuple[bool, List[Optional[bytes]], bytes, bytes]:
+        """``dm_repair_buffer``: the missing fragments of every segment from the ones given.
+        ``frags``: nseg x (data + parity) fragments, flat or one list per segment, ``None`` =
+        missing.  ``want`` (same shape, truthy = wanted; default: every missing fragment): a wanted
+        fragment that is given is checked against its name and rebuilt if it fails.  Returns (ok,
+        per fragment the rebuilt bytes or None, fragment statuses, segment statuses); a rebuilt
+        fragment is returned only when its SHA-256 equals its name.  ``out``: one ctypes buffer of a
+        fragment's size per fragment (flat) to receive the wanted ones instead; the library leaves
+        the buffer of a fragment it does not deliver untouched."""
+        total = self.k + self.m
+        flat = [f for seg in frags for f in seg] if frags and isinstance(frags[0], (list, tuple)) else list(frags)
+        if len(flat) % total:
+            raise DeossMerkleError(DM_ERR_INVALID, "need data + parity entries per segment")
+        if want is None:
+            wflat = [f is None for f in flat]
+        else:
+            wflat = [w for seg in want for w in seg] if want and isinstance(want[0], (list, tuple)) else list(want)
+        if len(wflat) != len(flat):
+            raise DeossMerkleError(DM_ERR_INVALID, "want needs one entry per fragment")
+        nseg = len(flat) // total
+        keep = [ctypes.create_string_buffer(bytes(f), len(f)) if f is not None else None for f in flat]
+        for b in keep:
+            if b is not None and len(b) != self.frag:
+                raise DeossMerkleError(DM_ERR_INVALID, "fragment sizes do not match")
+        if out is not None:
+            outs = [o if w else None for o, w in zip(out, wflat)]
+        else:
+            outs = [ctypes.create_string_buffer(self.frag) if w else None for w in wflat]
+        n = max(len(flat), 1)
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) if b is not None else None for b in keep])
+        optrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) if b is not None else None for b in outs])
+        fst = ctypes.create_string_buffer(max(nseg * total, 1))
+        sst = ctypes.create_string_buffer(max(nseg, 1))
+        ok = ctypes.c_int(0)
+        self._check(self.ctx._L.dm_repair_buffer(self.enc._h, ptrs, optrs, frag_names, nseg, self.segment, fst, sst,
+                                                 ctypes.byref(ok)), "dm_repair_buffer")
+        st = fst.raw[:nseg * total]
+        got = [o.raw if (o is not None and st[i] == 4) else None for i, o in enumerate(outs)]
+        return bool(ok.value), got, st, sst.raw[:nseg]
+
+    def repair_files(self, fragdir: str, frag_names: bytes, scrub: bool = False) -> Tuple[bool, int, bytes, bytes]:
+        """``dm_repair_files``: make the fragment directory ``fragdir/<hex name>`` whole again.  A
+        file that is missing or has the wrong length is rebuilt from its segment's other fragments;
+        with ``scrub`` every existing file is read and checked too and a bad one is replaced.
+        Returns (ok, files rebuilt, fragment statuses, segment statuses)."""
+        total = self.k + self.m
+        nseg = len(frag_names) // (32 * total)
+        fst = ctypes.create_string_buffer(max(nseg * total, 1))
+        sst = ctypes.create_string_buffer(max(nseg, 1))
+        ok, nre = ctypes.c_int(0), ctypes.c_uint64(0)
+        L = self.ctx._L
+        rc = L.dm_repair_files(self.enc._h, os.fsencode(fragdir), frag_names, nseg, self.segment,
+                               REPAIR_SCRUB if scrub else 0, fst, sst, ctypes.byref(nre), ctypes.byref(ok))
+        if rc == DM_ERR_IO:   # file errors keep Go's text
+            raise DeossMerkleError(rc, (L.dm_last_error(None) or b"").decode())
+        self._check(rc, "dm_repair_files")
+        return bool(ok.value), nre.value, fst.raw[:nseg * total], sst.raw[:nseg]
+
+    def RepairFragments(self, fragdir: str, segments: List[SegmentDataInfo], scrub: bool = False
+                        ) -> Tuple[int, Optional[Exception]]:
+        """process.RepairFragments (go/process/repair_hip.go): ``segments`` is what FullProcessing
+        returned; every fragment file of theirs that is missing from ``fragdir`` (with ``scrub``:
+        or does not equal its name) is rebuilt from the segment's other fragments.  Needs neither
+        the object nor the cipher.  (files rebuilt, None), or (files rebuilt, error) when some
+        segment has too few good fragments left."""
+        total = self.k + self.m
+        try:
+            fragn = b"".join(bytes.fromhex(os.path.basename(f)) for s in segments for f in s.FragmentHash)
+            if len(fragn) != 32 * total * len(segments):
+                raise ValueError("fragment names must be hex SHA-256")
+            ok, n, _, sst = self.repair_files(fragdir, fragn, scrub)
+        except (OSError, ValueError, DeossMerkleError) as e:
+            return 0, e
+        if not ok:
+            bad = [s for s in range(len(sst)) if sst[s]]
+            return n, DeossMerkleError(DM_ERR_INVALID, "repair failed: segment(s) %s could not be rebuilt from "
+                                       "verified fragments" % ", ".join(map(str, bad)))
+        return n, None
+
     def FullProcessing(self, file: str, cipher: str, savedir: str
                        ) -> Tuple[Optional[List[SegmentDataInfo]], str, Optional[Exception]]:
         """FullProcessing in one library call (``dm_full_processing``: reads, coding, hashing and
@@ -509,6 +592,18 @@ def RestoreFile(fragdir: str, segments: List[SegmentDataInfo], size: int, out_pa
         except DeossMerkleError as e:   # no GPU: fails the Go way, as FullProcessing
             return False, e
     return _default.RestoreFile(fragdir, segments, size, out_path, cipher)
+
+
+def RepairFragments(fragdir: str, segments: List[SegmentDataInfo], scrub: bool = False
+                    ) -> Tuple[int, Optional[Exception]]:
+    """process.RepairFragments on the default GPU pipeline (Processor.RepairFragments)."""
+    global _default
+    if _default is None:
+        try:
+            _default = Processor()
+        except DeossMerkleError as e:   # no GPU: fails the Go way, as FullProcessing
+            return 0, e
+    return _default.RepairFragments(fragdir, segments, scrub)
 
 
 def FindFragment(fpath: str, fragment_hash: str) -> Tuple[Optional[bytes], Optional[Exception]]:

@@ -161,6 +161,48 @@ class Encoder:
                     "dm_rs_restore_device_async")
 
 
+    def repair_device_async(self, frag_ptrs: Sequence[int], present: Sequence[bool], nseg: int, frag: int,
+                            stream: int = 0) -> None:
+        """``dm_rs_repair_device_async``: ``nseg`` segments, each with its own pattern, in one kernel
+        launch.  ``frag_ptrs``: nseg x total device addresses of ``frag`` bytes each; ``present``
+        truthy: holds the fragment; falsy with an address: wanted, written; 0 / None: absent and
+        not wanted."""
+        n = nseg * self.total_shards
+        if len(frag_ptrs) != n or len(present) != n:
+            raise DeossMerkleError(-2, "need one pointer and one flag per fragment of every segment")
+        ptrs = (ctypes.c_void_p * n)(*[p or None for p in frag_ptrs])
+        pres = bytes(int(bool(p)) for p in present)
+        self._check(self._L.dm_rs_repair_device_async(self._h, ptrs, pres, nseg, frag, stream),
+                    "dm_rs_repair_device_async")
+
+
+def repair_plan(present: Sequence[bool], want: Optional[Sequence[bool]] = None,
+                data_shards: int = DATA_SHARDS, parity_shards: int = PAR_SHARDS
+                ) -> Tuple[List[int], List[int], List[List[int]]]:
+    """``dm_rs_repair_plan`` (pure host function, no GPU): for one pattern the fragments read (the
+    first ``data_shards`` present in index order), the fragments written -- every one that is
+    wanted (default: all) and not present, data or parity -- and one coding row per output.
+    Raises :class:`ErrTooFewShards`."""
+    from ._lib import load_library
+    L = load_library()
+    k, t = data_shards, data_shards + parity_shards
+    if len(present) != t or (want is not None and len(want) != t):
+        raise DeossMerkleError(-2, "present and want need data + parity entries")
+    ins, outs = (ctypes.c_int * k)(), (ctypes.c_int * parity_shards)()
+    rows = ctypes.create_string_buffer(parity_shards * k)
+    nout = ctypes.c_int()
+    pres = bytes(int(bool(p)) for p in present)
+    wnt = bytes(int(bool(p)) for p in want) if want is not None else None
+    rc = L.dm_rs_repair_plan(k, parity_shards, pres, wnt, ins, outs, rows, ctypes.byref(nout))
+    if rc != 0:
+        detail = (L.dm_last_error(None) or b"").decode()
+        if "too few shards" in detail:
+            raise ErrTooFewShards(rc, detail)
+        raise DeossMerkleError(rc, detail)
+    n = nout.value
+    return list(ins), list(outs[:n]), [list(rows.raw[i * k:(i + 1) * k]) for i in range(n)]
+
+
 def restore_plan(present: Sequence[bool], in_place: Optional[Sequence[bool]] = None,
                  data_shards: int = DATA_SHARDS, parity_shards: int = PAR_SHARDS
                  ) -> Tuple[List[int], List[int], List[List[int]]]:

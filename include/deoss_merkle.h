@@ -329,6 +329,57 @@ int dm_retrieve_file(dm_rs *rs, const char *fragdir, const uint8_t *frag_names, 
                      const uint8_t *fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
                      const char *out_path, uint8_t *frag_status, uint8_t *seg_status, int *ok);
 
+/* ---- repair: the storage side (DeOSS node/tracker.go:320-355, checkFileState -> reFullProcessing)
+ * Any `data` of a segment's fragments rebuild the others, data or parity; fragments are ciphertext
+ * already and each is named by its own SHA-256, so a lost fragment comes back without the object and
+ * without the cipher, and a rebuilt one proves itself.
+ *
+ * dm_rs_repair_plan: the plan of one pattern (pure host function, as dm_rs_restore_plan).
+ * present[data + parity]: 1 = usable; want[data + parity] (nullable = every missing fragment): 1 =
+ * rebuild it if it is not present.  inputs[data]: the first `data` present fragments in index order;
+ * outputs[*nout]: every fragment j with want[j] && !present[j] in index order (room for `parity`);
+ * rows: *nout x data coding rows (room for parity x data) -- row j of the inverse of the inputs'
+ * sub-matrix for a data fragment, (coding matrix row j) x that inverse for a parity fragment.
+ * Errors are dm_rs_restore_plan's. */
+int dm_rs_repair_plan(int data, int parity, const uint8_t *present, const uint8_t *want, int *inputs,
+                      int *outputs, uint8_t *rows, int *nout);
+/* Many segments, each with its own pattern, in ONE kernel launch on `stream`.  dev_frags: host
+ * array of nseg x (data + parity) device pointers to `frag` bytes each, 16-byte aligned;
+ * present[i] = 1: holds the fragment; present[i] = 0 and pointer non-NULL: wanted, written; NULL:
+ * absent and not wanted.  frag: a non-zero multiple of 16.  No verification.  Nothing wanted:
+ * nothing is launched.  Too few present in any segment: DM_ERR_INVALID "too few shards given ..."
+ * before anything is launched. */
+int dm_rs_repair_device_async(dm_rs *rs, void *const *dev_frags, const uint8_t *present, uint64_t nseg,
+                              uint64_t frag, void *stream);
+/* Host fragments in, verified rebuilt fragments out (synchronous, one call lane).  frags, out: nseg x
+ * (data + parity) host pointers to segment/data bytes each.  frags[i] NULL = missing; out[i] non-NULL
+ * = wanted: it receives fragment i if that was missing or failed its name, and only when the rebuilt
+ * bytes' SHA-256 equals frag_names[i] (required); otherwise out[i] is untouched.  Per segment that
+ * needs anything the first `data` fragments given are the inputs; ONE repair launch, then ONE leaf
+ * launch over inputs and outputs.  An input that fails its name is bad: its segment's outputs are
+ * discarded and the next fragment given takes its place in another round (at most parity + 1).  A
+ * given fragment with out[i] set is checked even when it is no input.
+ * frag_status[s*(data+parity)+j] (nullable): 0 absent (still) or never looked at, 1 used as input and
+ * verified, 2 verified but not needed, 3 bad (and still bad if it could not be rebuilt), 4 rebuilt,
+ * verified and delivered.  seg_status[s] (nullable): 0 ok, 1 too few good fragments, 2 every input
+ * verified but an output does not equal its name (that output is not delivered).
+ * *ok = 1 iff every wanted fragment that was missing or bad was delivered; a failed repair is a
+ * result (DM_OK, *ok = 0), and the verified fragments of other segments are delivered all the same.
+ * nseg == 0: DM_ERR_EMPTY.  With dm_set_timing every round adds one record to dm_timing_summary. */
+int dm_repair_buffer(dm_rs *rs, const void *const *frags, void *const *out, const uint8_t *frag_names,
+                     uint64_t nseg, uint64_t segment, uint8_t *frag_status, uint8_t *seg_status, int *ok);
+#define DM_REPAIR_SCRUB 1   /* also read and check every existing fragment file, rebuild the bad ones */
+/* The same on the directory dm_full_processing writes: fragdir/<lower-case hex name>.  A file that
+ * does not exist, or has the wrong length, is missing and wanted.  Without DM_REPAIR_SCRUB an
+ * existing file of the right length is read only as an input, and a segment with all its files costs
+ * one stat per file.  Each rebuilt fragment is written under a temporary name and renamed to its hex
+ * name after its digest matched (replacing a bad file); no temporary file is left behind.  Several
+ * fragments may share a name (the zero tail of a padded last segment): one file serves them all, a
+ * missing one is written once and every owner reports 4.  *nrebuilt (nullable): files written.
+ * Works in windows of segments through the pinned slots.  I/O errors keep Go's texts. */
+int dm_repair_files(dm_rs *rs, const char *fragdir, const uint8_t *frag_names, uint64_t nseg, uint64_t segment,
+                    int flags, uint8_t *frag_status, uint8_t *seg_status, uint64_t *nrebuilt, int *ok);
+
 /* ---- the cipher branch: FullProcessing(file, cipher != "", savedir) and Retrievefile(..., cipher)
  * PARITY-UNPINNED: the scheme is restated from recollection of cess-go-sdk core/process and
  * utils.AesCbcEncrypt / AesCbcDecrypt (deoss_amd/csrc/cipher_scheme.hpp); the

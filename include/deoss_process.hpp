@@ -281,6 +281,45 @@ inline std::optional<Error> RestoreFile(const std::string& fragdir, const std::v
     return std::nullopt;
 }
 
+// RepairFragments(fragDir, segs, scrub) (go/process/repair_hip.go): what DeOSS's tracker needs when
+// a fragment file went missing (node/tracker.go:320-355), without the object and without the
+// cipher.  segs is what FullProcessing returned; every fragment file of theirs that is missing from
+// fragDir or has the wrong length -- with scrub: or does not equal its name -- is rebuilt from the
+// other fragments of its segment (dm_repair_files) and appears under its name only after its
+// SHA-256 matched.  first: files rebuilt, also when some segment had too few good fragments left.
+inline std::pair<uint64_t, std::optional<Error>> RepairFragments(const std::string& fragdir,
+                                                                 const std::vector<SegmentDataInfo>& segs,
+                                                                 bool scrub = false) {
+    auto base32 = [](const std::string& path, uint8_t* out) -> bool {
+        const std::string n = path.substr(path.rfind('/') == std::string::npos ? 0 : path.rfind('/') + 1);
+        auto nib = [](char ch) -> int { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : -1; };
+        if (n.size() != 64) return false;
+        for (int i = 0; i < 32; i++) {
+            const int hi = nib(n[2 * i]), lo = nib(n[2 * i + 1]);
+            if (hi < 0 || lo < 0) return false;
+            out[i] = (uint8_t)(hi * 16 + lo);
+        }
+        return true;
+    };
+    const int total = DataShards + ParShards;
+    std::vector<uint8_t> fragn(32 * segs.size() * total);
+    for (size_t s = 0; s < segs.size(); s++) {
+        bool ok = (int)segs[s].FragmentHash.size() == total;
+        for (int j = 0; ok && j < total; j++) ok = base32(segs[s].FragmentHash[j], fragn.data() + 32 * (s * total + j));
+        if (!ok) return {0, Error{DM_ERR_INVALID, "process: fragment names must be hex SHA-256"}};
+    }
+    auto& p = Pipelines::instance();
+    dm_rs* rs = p.pick();
+    if (!rs) return {0, Error{p.status(), dm_strerror(p.status())}};
+    int ok = 0;
+    uint64_t n = 0;
+    const int rc = dm_repair_files(rs, fragdir.c_str(), fragn.data(), segs.size(), SegmentSize, scrub ? DM_REPAIR_SCRUB : 0,
+                                   nullptr, nullptr, &n, &ok);
+    if (rc != DM_OK) return {n, last_error(rc)};
+    if (!ok) return {n, Error{DM_ERR_INVALID, "process: repair failed: too few verified fragments or a fragment mismatch"}};
+    return {n, std::nullopt};
+}
+
 // FullProcessing while the body arrives (dm_pstream_*): Write the pieces, then Close.
 class Writer {
   public:
