@@ -42,6 +42,7 @@ EXPORTS = (
     "dm_rs_repair_plan", "dm_rs_repair_device_async", "dm_repair_buffer", "dm_repair_files",
     "dm_aes_cbc_encrypt_device_async", "dm_aes_cbc_decrypt_device_async", "dm_process_cipher_buffer",
     "dm_restore_cipher_buffer",
+    "dm_range_plan", "dm_aes_cbc_decrypt_windows_device_async", "dm_restore_range_buffer", "dm_retrieve_range",
     "dm_pstream_open", "dm_pstream_write", "dm_pstream_close", "dm_pstream_abort",
     "dm_tree_node_count", "dm_tree_depth", "dm_tree_levels_device_async", "dm_tree_levels",
     "dm_merkle_paths_device_async", "dm_merkle_paths", "dm_verify_paths_device_async", "dm_verify_paths",
@@ -50,6 +51,18 @@ EXPORTS = (
     "dm_batcher_last_error",
     "dm_plan_shards", "dm_plan_route", "dm_route_constants", "dm_pstream_stats", "dm_exchange_timing", "dm_last_call_devices",
 )
+
+
+class RangeWindow(ctypes.Structure):
+    """dm_range_window: bytes [first, first + bytes) of segment ``seg`` read on the device."""
+    _fields_ = [("seg", ctypes.c_uint64), ("first", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class AesWindow(ctypes.Structure):
+    """dm_aes_window: one window of a CBC chain on the device."""
+    _fields_ = [("inp", ctypes.c_void_p), ("prev", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("nblk", ctypes.c_uint64), ("check_pad", ctypes.c_int)]
 
 
 class DeossMerkleError(RuntimeError):
@@ -130,6 +143,12 @@ def _declare(L: ctypes.CDLL) -> None:
         "dm_process_cipher_buffer": ([vp, vp, u64, u64, vp, u64, vp, vp, vp, vp], i32),
         "dm_restore_cipher_buffer": ([vp, pvp, vp, vp, vp, u64, u64, u64, i32, vp, u64, vp, vp, vp,
                                       ctypes.POINTER(i32)], i32),
+        "dm_range_plan": ([u64, u64, u64, i32, i32, u64, u64, i32, pu64, pu64, vp, u64, vp, u64, pu64], i32),
+        "dm_aes_cbc_decrypt_windows_device_async": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
+        "dm_restore_range_buffer": ([vp, pvp, vp, u64, u64, u64, u64, u64, i32, vp, u64, vp, vp, vp,
+                                     ctypes.POINTER(i32)], i32),
+        "dm_retrieve_range": ([vp, ctypes.c_char_p, vp, u64, u64, u64, u64, u64, i32, vp, u64, vp, vp, vp,
+                               ctypes.POINTER(i32)], i32),
         "dm_pstream_open": ([vp, u64, ctypes.c_char_p, i32, ctypes.POINTER(vp)], i32),
         "dm_pstream_write": ([vp, vp, u64], i32),
         "dm_pstream_close": ([vp, vp, vp, u64, pu64, vp], i32),

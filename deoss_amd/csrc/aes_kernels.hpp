@@ -11,6 +11,9 @@
 //       block, x over a segment's blocks and y over segments (launch_rs's grid), 16-byte loads,
 //       non-temporal 16-byte stores, out of place and compacting (the padding block is checked,
 //       not written).
+//   aes_cbc_decrypt_window_kernel  the same per block, over a table of windows that may start in
+//       the middle of a chain (each names its predecessor block) and differ in length: the ranged
+//       restore (range_capi.inl).
 //   aes_cbc_encrypt_kernel  C_i = E(P_i ^ C_{i-1}) is one serial chain per segment.  FOUR lanes (a
 //       DPP quad) carry a chain, lane j the state column j: it looks its own four bytes up in the
 //       four tables, and ShiftRows is three quad_perm reads of the neighbours' lookups (xor-ed on
@@ -199,6 +202,70 @@ void aes_cbc_decrypt_kernel(AesDecArgs a) {
                 rs_store(out + u * 16, x);
             else
                 a.pad_ok[seg] = (x.x == kAesPadWord && x.y == kAesPadWord && x.z == kAesPadWord && x.w == kAesPadWord) ? 1 : 0;
+        }
+    }
+}
+
+// ---- windows: decryption that starts in the middle of a chain (ranged restore, range_capi.inl) ----
+
+// One window of a CBC chain: nblk ciphertext blocks at `in`, their plaintext to `out`.  P_i needs
+// C_{i-1} only, so a window needs its predecessor block and nothing else of the chain; that block
+// has an address of its own (it may lie in another buffer), null = the IV.
+struct AesWindow {
+    const uint8_t* in;
+    const uint8_t* prev;
+    uint8_t* out;
+    uint64_t nblk;        // >= 1; >= 2 with check_pad
+    uint32_t check_pad;   // the last block is a padding block: its verdict goes to pad_ok[w], it is not stored
+    uint32_t pad_;
+};
+
+struct AesWinArgs {
+    AesKey rk;              // equivalent-inverse-cipher keys
+    uint32_t iv[4];
+    const AesWindow* win;   // [nwin], device memory
+    uint64_t nwin;
+    uint8_t* pad_ok;        // [nwin]; written for check_pad windows only
+};
+
+// Grid: x strides over a window's blocks, y over windows (rs_grid for the longest window; a shorter
+// one leaves lanes idle).  One lane per block as aes_cbc_decrypt_kernel; the descriptor is uniform
+// over the workgroup and read once per window.
+template <int NR>
+__global__ __launch_bounds__(kAesDecThreads)
+void aes_cbc_decrypt_window_kernel(AesWinArgs a) {
+    __shared__ uint32_t tab[5 * 256];
+    aes_fill_lds<kAesDecThreads>(tab, kAesTables.td0, kAesTables.inv);
+    const uint64_t ustride = (uint64_t)gridDim.x * kAesDecThreads;
+    const uint4 iv = make_uint4(a.iv[0], a.iv[1], a.iv[2], a.iv[3]);
+    for (uint64_t w = blockIdx.y; w < a.nwin; w += gridDim.y) {
+        const AesWindow d = a.win[w];
+        const uint64_t nstore = d.nblk - (d.check_pad ? 1 : 0);
+        uint64_t u = (uint64_t)blockIdx.x * kAesDecThreads + threadIdx.x;
+        // register double buffer: the next stride's loads are in flight while this block is decrypted
+        uint4 nc = iv, np = iv;
+        if (u < d.nblk) {
+            nc = aes_load16(d.in + u * 16);
+            if (u)
+                np = aes_load16(d.in + (u - 1) * 16);
+            else if (d.prev)
+                np = aes_load16(d.prev);
+        }
+        for (; u < d.nblk; u += ustride) {
+            const uint4 cblk = nc, prev = np;
+            if (u + ustride < d.nblk) {
+                nc = aes_load16(d.in + (u + ustride) * 16);
+                np = aes_load16(d.in + (u + ustride - 1) * 16);
+            }
+            uint4 x = aes_decrypt_block<NR>(cblk, a.rk, tab);
+            x.x ^= prev.x;
+            x.y ^= prev.y;
+            x.z ^= prev.z;
+            x.w ^= prev.w;
+            if (u < nstore)
+                rs_store(d.out + u * 16, x);
+            else
+                a.pad_ok[w] = (x.x == kAesPadWord && x.y == kAesPadWord && x.z == kAesPadWord && x.w == kAesPadWord) ? 1 : 0;
         }
     }
 }

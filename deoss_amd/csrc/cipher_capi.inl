@@ -1,5 +1,6 @@
 // cipher_capi.inl -- AES-CBC on the GPU (dm_aes_cbc_*_device_async; include/deoss_merkle.h) and the
-// launch helpers dm_process_cipher_buffer / dm_restore_cipher_buffer use.  Part of merkle_capi.hip
+// launch helpers dm_process_cipher_buffer / dm_restore_cipher_buffer and the ranged restore
+// (range_capi.inl: windows of chains) use.  Part of merkle_capi.hip
 // (after rs_capi.inl: the decrypt kernel shares rs_grid and rs_store).
 //
 // The cipher branch of cess-go-sdk process.FullProcessing / Retrievefile (cipher != ""): the scheme
@@ -77,9 +78,63 @@ hipError_t launch_aes_decrypt(Dev& d, hipStream_t s, const CipherKey& k, const u
     return hipGetLastError();
 }
 
+// Windows of chains (aes_cbc_decrypt_window_kernel): the descriptors are uploaded through the lane's
+// bounce buffer to d.aes_win, ONE launch decrypts them all.  pad_ok: [win.size()] on the device.
+int launch_aes_decrypt_windows(dm_ctx* c, Dev& d, hipStream_t s, const CipherKey& k, const std::vector<dm::AesWindow>& win,
+                               uint8_t* pad_ok) {
+    if (win.empty()) return DM_OK;
+    uint64_t longest = 0;
+    for (const dm::AesWindow& w : win) longest = std::max(longest, w.nblk);
+    const uint64_t bytes = win.size() * sizeof(dm::AesWindow);
+    RC_TRY(tables_begin(c, d, bytes + 1024));
+    RC_TRY(upload(c, d, s, d.aes_win, win.data(), bytes));
+    dm::AesWinArgs a{};
+    std::memcpy(a.rk.w, k.ks.dec, sizeof a.rk.w);
+    std::memcpy(a.iv, k.iv, 16);
+    a.win = static_cast<const dm::AesWindow*>(d.aes_win.p);
+    a.nwin = win.size();
+    a.pad_ok = pad_ok;
+    const dim3 grid = rs_grid(d, longest, a.nwin), block(dm::kAesDecThreads);
+    aes_for_rounds(k.ks.rounds, [&](auto NR) {
+        hipLaunchKernelGGL(dm::aes_cbc_decrypt_window_kernel<decltype(NR)::value>, grid, block, 0, s, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return DM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dm_aes_cbc_decrypt_windows_device_async(dm_ctx* ctx, const void* key, uint64_t key_len, const uint8_t iv[16],
+                                            const dm_aes_window* windows, uint64_t nwin, void* dev_pad_ok, void* stream) {
+    if (!ctx || !key || !iv) return bad_arg();
+    const int g = device_of(ctx, nwin && windows ? windows[0].in : nullptr);
+    CallLock lk(ctx, g, kReserved);
+    dm_ctx* c = ctx;
+    CipherKey k;
+    if (!dm_aes::expand_key(static_cast<const uint8_t*>(key), key_len, k.ks))
+        return fail(c, DM_ERR_INVALID, "%s", dm_cipher::kKeyLenError);
+    cipher_set_iv(k, iv);
+    if (nwin == 0) return DM_OK;
+    if (!windows) return fail(c, DM_ERR_INVALID, "dm_aes_cbc_decrypt_windows_device_async: null windows");
+    std::vector<dm::AesWindow> win(nwin);
+    for (uint64_t w = 0; w < nwin; w++) {
+        const dm_aes_window& x = windows[w];
+        const bool pad = x.check_pad != 0;
+        if (!x.in || !x.out || !is_aligned16(x.in) || !is_aligned16(x.prev) || !is_aligned16(x.out) ||
+            x.nblk < (pad ? 2u : 1u) || (pad && !dev_pad_ok))
+            return fail(c, DM_ERR_INVALID,
+                        "dm_aes_cbc_decrypt_windows_device_async: window %llu needs 16-byte aligned in, prev and out, "
+                        "nblk >= 1 (>= 2 and a verdict buffer with check_pad)", (unsigned long long)w);
+        win[w] = dm::AesWindow{static_cast<const uint8_t*>(x.in), static_cast<const uint8_t*>(x.prev),
+                               static_cast<uint8_t*>(x.out), x.nblk, pad ? 1u : 0u, 0u};
+    }
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    return launch_aes_decrypt_windows(c, d, s, k, win, static_cast<uint8_t*>(dev_pad_ok));
+}
 
 int dm_aes_cbc_encrypt_device_async(dm_ctx* ctx, const void* key, uint64_t key_len, const uint8_t iv[16], void* dev,
                                     uint64_t stride, uint64_t plain, uint64_t nseg, void* stream) {

@@ -13,7 +13,33 @@ import ctypes
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
-from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, DeossMerkleError, load_library
+from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, AesWindow, DeossMerkleError, RangeWindow, load_library
+
+RANGE_NO_PADDING_CHECK = 8                                          # DM_RANGE_NO_PADDING_CHECK
+RANGE_WIN_PREV_IV, RANGE_WIN_CHECK_PAD, RANGE_WIN_PAD_ONLY = 1, 2, 4   # DM_RANGE_WIN_*
+
+
+def range_plan(size: int, nseg: int, segment: int, data_shards: int, off: int, length: int, cipher: bool = False,
+               flags: int = 0) -> Tuple[int, int, List[List[int]], List[Tuple[int, int, int, int]]]:
+    """``dm_range_plan`` (pure host function, no GPU): what bytes [off, off + length) of an object of
+    ``size`` plaintext bytes in ``nseg`` segments need.  Returns (seg0, ntouched, need, windows):
+    ``need[t][j]`` = 1 when data fragment j of segment seg0 + t is needed, ``windows`` =
+    [(segment, first byte, byte count, RANGE_WIN_* flags)] read on the device.  A gateway fetches
+    exactly the ``need`` fragments (any ``data_shards`` of a segment's instead, where one is lost)."""
+    L = load_library()
+    seg0, nt, nw = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    head = (size, nseg, segment, data_shards, int(bool(cipher)), off, length, flags, ctypes.byref(seg0), ctypes.byref(nt))
+
+    def check(rc):
+        if rc != 0:
+            raise DeossMerkleError(rc, (L.dm_last_error(None) or b"").decode())
+    check(L.dm_range_plan(*head, None, 0, None, 0, ctypes.byref(nw)))
+    need = ctypes.create_string_buffer(max(nt.value * data_shards, 1))
+    win = (RangeWindow * max(nw.value, 1))()
+    check(L.dm_range_plan(*head, need, nt.value * data_shards, win, nw.value, ctypes.byref(nw)))
+    k = data_shards
+    return (seg0.value, nt.value, [list(need.raw[t * k:(t + 1) * k]) for t in range(nt.value)],
+            [(w.seg, w.first, w.bytes, w.flags) for w in win[:nw.value]])
 
 
 class MerkleContext:
@@ -222,6 +248,20 @@ class MerkleContext:
                                                             ctypes.c_void_p(dev_pad_ok),
                                                             ctypes.c_void_p(stream or None)),
                     "dm_aes_cbc_decrypt_device_async")
+
+    def aes_cbc_decrypt_windows_device_async(self, key: bytes, iv: bytes, windows, dev_pad_ok: int = 0,
+                                             stream: int = 0) -> None:
+        """``dm_aes_cbc_decrypt_windows_device_async``: ONE launch over ``windows`` =
+        [(dev_in, dev_prev or 0 for the IV, dev_out, nblk, check_pad)]; a check_pad window's verdict
+        goes to dev_pad_ok[w] and its last block is not stored."""
+        if len(iv) != 16:
+            raise DeossMerkleError(DM_ERR_INVALID, "iv must be 16 bytes")
+        arr = (AesWindow * max(len(windows), 1))(*[AesWindow(i or None, p or None, o or None, n, int(bool(c)))
+                                                    for i, p, o, n, c in windows])
+        self._check(self._L.dm_aes_cbc_decrypt_windows_device_async(self._h, bytes(key), len(key), bytes(iv), arr,
+                                                                    len(windows), ctypes.c_void_p(dev_pad_ok or None),
+                                                                    ctypes.c_void_p(stream or None)),
+                    "dm_aes_cbc_decrypt_windows_device_async")
 
     # -- tree levels and proofs (merkletree GetMerklePath / VerifyContent / VerifyTree) ----------
     def tree_node_count(self, n: int) -> int:

@@ -33,7 +33,7 @@ from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
 from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, DM_ERR_IO, DeossMerkleError
-from .merkle import MerkleContext
+from .merkle import RANGE_NO_PADDING_CHECK, MerkleContext, range_plan  # noqa: F401
 from .reedsolomon import DATA_SHARDS, PAR_SHARDS, Encoder
 
 SEGMENT_SIZE = 32 << 20                       # chain.SegmentSize
@@ -319,6 +319,97 @@ class Processor:
                                            "from verified fragments" % ", ".join(map(str, bad)))
         return True, None
 
+    # -- ranged restore (the HTTP Range of GET /file/open) -------------------------------------------
+    def _nseg_of(self, size: int, key: bytes) -> int:
+        piece = self.segment - CIPHER_BLOCK if key else self.segment
+        return (size + piece - 1) // piece
+
+    def range_plan(self, size: int, off: int, length: int, cipher=b"", padding_check: bool = True):
+        """``dm_range_plan`` for this pipeline's shape: (seg0, ntouched, need, windows) of bytes
+        [off, off + length) -- what a gateway fetches before :meth:`restore_range`."""
+        key = _cipher_bytes(cipher)
+        return range_plan(size, self._nseg_of(size, key), self.segment, self.k, off, length, bool(key),
+                          0 if padding_check else RANGE_NO_PADDING_CHECK)
+
+    def restore_range(self, frags, size: int, off: int, length: int, frag_names: Optional[bytes] = None,
+                      cipher=b"", padding_check: bool = True, flags: int = RESTORE_VERIFY_FRAGMENTS, out=None
+                      ) -> Tuple[bool, Optional[bytes], bytes, bytes]:
+        """``dm_restore_range_buffer``: bytes [off, off + length) of the object from just the fragments
+        that cover them.  ``frags`` and ``frag_names`` are shaped as :meth:`restore_buffer`'s, over
+        the whole object; fragments outside :meth:`range_plan`'s ``need`` may be ``None`` and are never
+        looked at unless a needed one is missing or bad.  Segment names and the fid are not checked
+        (they name whole segments).  Returns (ok, the bytes or None, fragment statuses, segment
+        statuses); with a ``cipher`` the first touched segment's padding block is checked too unless
+        ``padding_check`` is off (a wrong cipher: ``SEG_BAD_PADDING``, ``ok = False``)."""
+        total = self.k + self.m
+        key = _cipher_bytes(cipher)
+        flat = [f for seg in frags for f in seg] if frags and isinstance(frags[0], (list, tuple)) else list(frags)
+        if len(flat) % total:
+            raise DeossMerkleError(DM_ERR_INVALID, "need data + parity entries per segment")
+        nseg = len(flat) // total
+        keep = [ctypes.create_string_buffer(bytes(f), len(f)) if f is not None else None for f in flat]
+        for b in keep:
+            if b is not None and len(b) != self.frag:
+                raise DeossMerkleError(DM_ERR_INVALID, "fragment sizes do not match")
+        ptrs = (ctypes.c_void_p * max(len(flat), 1))(*[ctypes.addressof(b) if b is not None else None for b in keep])
+        dst = out if out is not None else ctypes.create_string_buffer(max(length, 1))
+        fst = ctypes.create_string_buffer(max(nseg * total, 1))
+        sst = ctypes.create_string_buffer(max(nseg, 1))
+        ok = ctypes.c_int(0)
+        if not padding_check:
+            flags |= RANGE_NO_PADDING_CHECK
+        self._check(self.ctx._L.dm_restore_range_buffer(self.enc._h, ptrs, frag_names, nseg, size, self.segment, off,
+                                                        length, flags, key or None, len(key), dst, fst, sst,
+                                                        ctypes.byref(ok)), "dm_restore_range_buffer")
+        data = dst.raw[:length] if (ok.value and out is None) else None
+        return bool(ok.value), data, fst.raw[:nseg * total], sst.raw[:nseg]
+
+    def retrieve_range(self, fragdir: str, frag_names: bytes, size: int, off: int, length: int, cipher=b"",
+                       padding_check: bool = True, flags: int = RESTORE_VERIFY_FRAGMENTS, out=None
+                       ) -> Tuple[bool, Optional[bytes], bytes, bytes]:
+        """``dm_retrieve_range``: the same from the fragment files ``fragdir/<hex name>``; no file is
+        written.  Returns as :meth:`restore_range`."""
+        total = self.k + self.m
+        key = _cipher_bytes(cipher)
+        nseg = len(frag_names) // (32 * total)
+        dst = out if out is not None else ctypes.create_string_buffer(max(length, 1))
+        fst = ctypes.create_string_buffer(max(nseg * total, 1))
+        sst = ctypes.create_string_buffer(max(nseg, 1))
+        ok = ctypes.c_int(0)
+        if not padding_check:
+            flags |= RANGE_NO_PADDING_CHECK
+        L = self.ctx._L
+        rc = L.dm_retrieve_range(self.enc._h, os.fsencode(fragdir), frag_names, nseg, size, self.segment, off, length,
+                                 flags, key or None, len(key), dst, fst, sst, ctypes.byref(ok))
+        if rc == DM_ERR_IO:   # file errors keep Go's text
+            raise DeossMerkleError(rc, (L.dm_last_error(None) or b"").decode())
+        self._check(rc, "dm_retrieve_range")
+        data = dst.raw[:length] if (ok.value and out is None) else None
+        return bool(ok.value), data, fst.raw[:nseg * total], sst.raw[:nseg]
+
+    def RestoreRange(self, fragdir: str, segments: List[SegmentDataInfo], size: int, off: int, length: int, cipher=""
+                     ) -> Tuple[Optional[bytes], Optional[Exception]]:
+        """Bytes [off, off + length) of the object ``segments`` describes (what FullProcessing
+        returned) from whichever of its fragments lie in ``fragdir``: only the fragments the range
+        needs are read, each checked against its name, a lost one rebuilt and checked.  (bytes, None),
+        or (None, error)."""
+        total = self.k + self.m
+        try:
+            fragn = b"".join(bytes.fromhex(os.path.basename(f)) for s in segments for f in s.FragmentHash)
+            if len(fragn) != 32 * total * len(segments):
+                raise ValueError("fragment names must be hex SHA-256")
+            ok, data, fst, sst = self.retrieve_range(fragdir, fragn, size, off, length, cipher=cipher)
+        except (OSError, ValueError, DeossMerkleError) as e:
+            return None, e
+        if not ok and any(st == SEG_BAD_PADDING for st in sst):
+            return None, DeossMerkleError(DM_ERR_INVALID, "restore failed: bad padding after decryption "
+                                          "(wrong cipher?)")
+        if not ok:
+            bad = [s for s in range(len(sst)) if sst[s]]
+            return None, DeossMerkleError(DM_ERR_INVALID, "restore failed: segment(s) %s could not be rebuilt "
+                                          "from verified fragments" % ", ".join(map(str, bad)))
+        return data, None
+
     # -- repair (the storage side) -------------------------------------------------------------------
     def repair_buffer(self, frags, frag_names: bytes, want=None, out=None
                       ) -> Tuple[bool, List[Optional[bytes]], bytes, bytes]:
@@ -592,6 +683,18 @@ def RestoreFile(fragdir: str, segments: List[SegmentDataInfo], size: int, out_pa
         except DeossMerkleError as e:   # no GPU: fails the Go way, as FullProcessing
             return False, e
     return _default.RestoreFile(fragdir, segments, size, out_path, cipher)
+
+
+def RestoreRange(fragdir: str, segments: List[SegmentDataInfo], size: int, off: int, length: int, cipher=""
+                 ) -> Tuple[Optional[bytes], Optional[Exception]]:
+    """A byte range of an object on the default GPU pipeline (Processor.RestoreRange)."""
+    global _default
+    if _default is None:
+        try:
+            _default = Processor()
+        except DeossMerkleError as e:   # no GPU: fails the Go way, as FullProcessing
+            return None, e
+    return _default.RestoreRange(fragdir, segments, size, off, length, cipher)
 
 
 def RepairFragments(fragdir: str, segments: List[SegmentDataInfo], scrub: bool = False

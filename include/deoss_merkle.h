@@ -421,6 +421,104 @@ int dm_restore_cipher_buffer(dm_rs *rs, const void *const *frags, const uint8_t 
                              const void *cipher, uint64_t cipher_len, void *out, uint8_t *frag_status,
                              uint8_t *seg_status, int *ok);
 
+/* ---- ranged restore: any byte range from just the fragments that cover it (the HTTP Range of
+ * GET /file/open, node/fileHandler.go:399-545, which otherwise restores the whole object first).
+ * A segment is the concatenation of its data fragments and every fragment is named by its own
+ * SHA-256, so bytes [off, off + len) need a few data fragments of a few segments, each checked on
+ * its own; a needed fragment that is missing or bad is rebuilt from any `data` others and must equal
+ * its name.  Segment names and the fid are NOT checked here: they name whole segments, which a
+ * ranged restore never has.  With a cipher (PARITY-UNPINNED: the scheme is recalled, not pinned, as
+ * above) every segment is its own CBC chain, and decrypting blocks b0 .. b1 needs ciphertext blocks
+ * max(b0 - 1, 0) .. b1 only.
+ *
+ * dm_range_plan: which segments, data fragments and bytes a range needs (pure host function: no GPU,
+ * no context; the runtime uses this same rule; a gateway calls it to decide what to fetch).
+ * size, nseg, segment, data: the object as for dm_restore_buffer (size = plaintext bytes; cipher != 0:
+ * pieces of segment - 16 bytes).  *seg0, *ntouched: the first touched segment and the count.
+ * need (nullable; need_cap >= *ntouched x data): need[t*data + j] = 1 when data fragment j of segment
+ * seg0 + t holds bytes of the range or, with a cipher, the block before them or the padding block
+ * that is checked.  windows (nullable; win_cap >= *nwin <= 2 x *ntouched): the bytes read on the
+ * device, by segment.  Without a cipher one window per touched segment: `first`, `bytes` of the
+ * segment, flags 0.  With one, the blocks decrypted: first = 16*b0, bytes = 16*(block count);
+ * DM_RANGE_WIN_PREV_IV: b0 = 0, the IV precedes it (otherwise the block at first - 16 does);
+ * DM_RANGE_WIN_CHECK_PAD: the window's last block is the segment's padding block, checked and not
+ * plaintext.  The padding is checked on the first touched segment (not with
+ * DM_RANGE_NO_PADDING_CHECK in flags) and on every segment whose range reaches data fragment
+ * data - 1 anyway: a window ending in the last plaintext block is extended by the padding block, any
+ * other such segment gets one more window of its last two blocks (DM_RANGE_WIN_PAD_ONLY: none of its
+ * blocks is part of the range; it follows the segment's range window).  Both output arrays NULL: a
+ * first call that learns *ntouched and *nwin.
+ * DM_ERR_INVALID: len == 0 or off + len > size (also on overflow); size not ending in the last of
+ * nseg pieces; a segment that is no multiple of 16 x data or, with a cipher, below 32 bytes; an
+ * output array that is too small. */
+#define DM_RANGE_NO_PADDING_CHECK 8   /* flags: no extra fragment for the wrong-cipher check (garbage on a wrong key) */
+#define DM_RANGE_WIN_PREV_IV 1
+#define DM_RANGE_WIN_CHECK_PAD 2
+#define DM_RANGE_WIN_PAD_ONLY 4
+typedef struct dm_range_window {
+    uint64_t seg;     /* segment of the object */
+    uint64_t first;   /* first byte read, within the segment */
+    uint64_t bytes;
+    uint32_t flags;   /* DM_RANGE_WIN_* */
+    uint32_t reserved;
+} dm_range_window;
+int dm_range_plan(uint64_t size, uint64_t nseg, uint64_t segment, int data, int cipher, uint64_t off, uint64_t len,
+                  int flags, uint64_t *seg0, uint64_t *ntouched, uint8_t *need, uint64_t need_cap,
+                  dm_range_window *windows, uint64_t win_cap, uint64_t *nwin);
+/* AES-CBC decryption of windows of chains in ONE launch on `stream`: a window may start in the
+ * middle of a chain and windows may differ in length.  windows: host array (uploaded through the
+ * call lane's scratch; it may be released on return).  in: the first ciphertext block; prev: the
+ * block before it, an address of its own (it may lie in another buffer), NULL = the IV; out: nblk
+ * plaintext blocks (no overlap with any input); check_pad != 0: the window's last block is a padding
+ * block: dev_pad_ok[w] (one byte per window; written for such windows only) is 1 iff it decrypts to
+ * sixteen 0x10 bytes, and it is not stored (nblk - 1 blocks reach out).  in, prev and out 16-byte
+ * aligned device addresses; nblk >= 1, >= 2 with check_pad.  nwin == 0 launches nothing. */
+typedef struct dm_aes_window {
+    const void *in;
+    const void *prev;
+    void *out;
+    uint64_t nblk;
+    int check_pad;
+} dm_aes_window;
+int dm_aes_cbc_decrypt_windows_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16],
+                                            const dm_aes_window *windows, uint64_t nwin, void *dev_pad_ok,
+                                            void *stream);
+/* Bytes [off, off + len) of an object from fragments in host memory (synchronous, one call lane).
+ * frags, frag_names, frag_status, seg_status: shaped exactly as dm_restore_buffer's, indexed over the
+ * WHOLE object (nseg x (data + parity)), so a caller switches between full and ranged restore with
+ * the same metadata; segments outside the range are never looked at.  cipher NULL / cipher_len 0: no
+ * cipher; `size` is the plaintext size.  flags: DM_RESTORE_VERIFY_FRAGMENTS (with frag_names),
+ * DM_RANGE_NO_PADDING_CHECK; the segment and fid flags are ignored (see above).
+ * Per touched segment, in rounds (at most parity + 1): when every needed data fragment (dm_range_plan)
+ * is given and not known bad, only those go to the device; otherwise the first `data` usable
+ * fragments in index order do, and the needed data fragments that are not usable -- no other -- are
+ * rebuilt in ONE repair launch for all segments.  Verifying, one leaf launch hashes what was
+ * brought (a mismatch is bad, status 3, and absent for the next round), one more the rebuilt
+ * fragments, which must equal their names.  With a cipher ONE window launch decrypts the range and
+ * checks the paddings the plan names.  `len` bytes reach `out` ONLY when every touched segment is 0
+ * and every check asked for held: *ok = 1; otherwise `out` is untouched and *ok = 0 -- a result, not
+ * an error (DM_OK).  With flags = 0 fragments are used as given.
+ * frag_status: 0 never looked at or absent, 1 used (and verified, when verifying), 2 verified but not
+ * needed in the end, 3 bad (a given fragment that is not its name: it stays 3 when its bytes were then
+ * rebuilt), 4 was absent, rebuilt (and verified).  seg_status: 0 ok (also every untouched
+ * segment), 1 too few good fragments, 2 a rebuilt fragment does not equal its name, 3 bad padding.
+ * Errors: dm_range_plan's and dm_restore_buffer's.  With dm_set_timing every round adds one record
+ * to dm_timing_summary. */
+int dm_restore_range_buffer(dm_rs *rs, const void *const *frags, const uint8_t *frag_names, uint64_t nseg,
+                            uint64_t size, uint64_t segment, uint64_t off, uint64_t len, int flags,
+                            const void *cipher, uint64_t cipher_len, void *out, uint8_t *frag_status,
+                            uint8_t *seg_status, int *ok);
+/* The same from fragment files fragdir/<lower-case hex name>, read as dm_retrieve_file reads them
+ * (frag_names required; a missing file is absent, one of the wrong length is bad; I/O errors keep
+ * Go's texts).  Works through the pinned slots in windows of touched segments
+ * (DEOSS_RT_WINDOW_BYTES), so device and pinned memory do not grow with len.  Nothing is written
+ * unless all is good: a range within one window leaves the device only after every check; a longer
+ * one is staged window by window in pageable host memory and copied to `out` at the end.  No file is
+ * written. */
+int dm_retrieve_range(dm_rs *rs, const char *fragdir, const uint8_t *frag_names, uint64_t nseg, uint64_t size,
+                      uint64_t segment, uint64_t off, uint64_t len, int flags, const void *cipher,
+                      uint64_t cipher_len, void *out, uint8_t *frag_status, uint8_t *seg_status, int *ok);
+
 /* FullProcessing while the upload body arrives (SURVEY.md 8f #1 + #2): the handlers write the body
  * to a file (node/objectHandler.go:248-266, node/fileHandler.go:899-937) and then run
  * FullProcessing(fpath, "", cacheDir) over it (node/objectHandler.go:168, node/fileHandler.go:771).

@@ -281,6 +281,53 @@ inline std::optional<Error> RestoreFile(const std::string& fragdir, const std::v
     return std::nullopt;
 }
 
+// RestoreRange(fragDir, segs, size, off, length, cipher) (go/process/range_hip.go): bytes
+// [off, off + length) of the object for the HTTP Range of GET /file/open (node/fileHandler.go:399-545),
+// from just the fragments that cover them (dm_retrieve_range; dm_range_plan says which, so a gateway
+// fetches only those).  Every fragment read is checked against its name, a lost one is rebuilt from
+// any DataShards others and must equal its name; segment names and the fid are not checked (they name
+// whole segments).  cipher: "" or the 16 / 24 / 32 bytes the object was processed with (the scheme
+// is recalled, not pinned: deoss_amd/csrc/cipher_scheme.hpp); size, off and length count plaintext.
+inline std::pair<std::vector<uint8_t>, std::optional<Error>> RestoreRange(const std::string& fragdir,
+                                                                           const std::vector<SegmentDataInfo>& segs,
+                                                                           uint64_t size, uint64_t off, uint64_t length,
+                                                                           const std::string& cipher = "") {
+    auto base32 = [](const std::string& path, uint8_t* out) -> bool {
+        const std::string n = path.substr(path.rfind('/') == std::string::npos ? 0 : path.rfind('/') + 1);
+        auto nib = [](char ch) -> int { return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : -1; };
+        if (n.size() != 64) return false;
+        for (int i = 0; i < 32; i++) {
+            const int hi = nib(n[2 * i]), lo = nib(n[2 * i + 1]);
+            if (hi < 0 || lo < 0) return false;
+            out[i] = (uint8_t)(hi * 16 + lo);
+        }
+        return true;
+    };
+    const int total = DataShards + ParShards;
+    std::vector<uint8_t> fragn(32 * segs.size() * total), sst(segs.size());
+    for (size_t s = 0; s < segs.size(); s++) {
+        bool ok = (int)segs[s].FragmentHash.size() == total;
+        for (int j = 0; ok && j < total; j++) ok = base32(segs[s].FragmentHash[j], fragn.data() + 32 * (s * total + j));
+        if (!ok) return {{}, Error{DM_ERR_INVALID, "process: fragment names must be hex SHA-256"}};
+    }
+    auto& p = Pipelines::instance();
+    dm_rs* rs = p.pick();
+    if (!rs) return {{}, Error{p.status(), dm_strerror(p.status())}};
+    std::vector<uint8_t> out(length ? length : 1);
+    int ok = 0;
+    const int rc = dm_retrieve_range(rs, fragdir.c_str(), fragn.data(), segs.size(), size, SegmentSize, off, length,
+                                     DM_RESTORE_VERIFY_FRAGMENTS, cipher.empty() ? nullptr : cipher.data(), cipher.size(),
+                                     out.data(), nullptr, sst.data(), &ok);
+    if (rc != DM_OK) return {{}, last_error(rc)};
+    if (!ok) {
+        for (uint8_t st : sst)
+            if (st == 3) return {{}, Error{DM_ERR_INVALID, "process: restore failed: bad padding after decryption (wrong cipher?)"}};
+        return {{}, Error{DM_ERR_INVALID, "process: restore failed: too few verified fragments or a rebuilt fragment mismatch"}};
+    }
+    out.resize(length);
+    return {std::move(out), std::nullopt};
+}
+
 // RepairFragments(fragDir, segs, scrub) (go/process/repair_hip.go): what DeOSS's tracker needs when
 // a fragment file went missing (node/tracker.go:320-355), without the object and without the
 // cipher.  segs is what FullProcessing returned; every fragment file of theirs that is missing from
