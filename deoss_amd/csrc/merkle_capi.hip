@@ -1689,7 +1689,8 @@ void no_sharding(dm_ctx* c, const char* why) {
                  "one GPU\n", c->nphys, why);
 }
 
-int ctx_create(dm_ctx** out, const int* devs, int ndev, int lanes) {
+// lanes_given: the caller asked for that many lanes (dm_create_lanes), not the default (dm_create).
+int ctx_create(dm_ctx** out, const int* devs, int ndev, int lanes, bool lanes_given) {
     if (!out || lanes < 1 || lanes > kMaxLanes) return bad_arg();
     *out = nullptr;
     DeviceRestore dev;
@@ -1707,7 +1708,9 @@ int ctx_create(dm_ctx** out, const int* devs, int ndev, int lanes) {
     const int nvirt = vd ? std::atoi(vd) : 0;
     if (nvirt > 1) {
         ids.assign((size_t)std::min(nvirt, 64), ids[0]);
-        lanes = 1;   // every virtual device stands for a GPU of its own
+        // every virtual device stands for a GPU of its own: one lane each, unless the caller asks for
+        // more (dm_create_lanes: the lane-major layout with nphys > 1 then runs on a one-GPU box)
+        if (!lanes_given) lanes = 1;
     }
     dm_ctx* c = new dm_ctx();
     c->nphys = (int)ids.size();
@@ -1765,12 +1768,12 @@ int dm_create(dm_ctx** out, const int* devs, int ndev) {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return set_err(DM_ERR_NODEV, "no usable GPU");
     if (first < 0 || first >= count) return bad_arg();
     std::lock_guard<std::mutex> lk(g_create_mu);
-    return ctx_create(out, devs, ndev, default_lanes(devs, ndev));
+    return ctx_create(out, devs, ndev, default_lanes(devs, ndev), false);
 }
 
 int dm_create_lanes(dm_ctx** out, const int* devs, int ndev, int lanes) {
     std::lock_guard<std::mutex> lk(g_create_mu);
-    return ctx_create(out, devs, ndev, lanes);
+    return ctx_create(out, devs, ndev, lanes, true);
 }
 
 int dm_can_shard(dm_ctx* ctx) { return ctx && ctx->nphys > 1 && (ctx->shard_ok || ctx->force_sharded) ? 1 : 0; }
