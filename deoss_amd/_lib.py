@@ -41,7 +41,7 @@ EXPORTS = (
     "dm_rs_restore_plan", "dm_rs_restore_device_async", "dm_restore_buffer", "dm_retrieve_file",
     "dm_rs_repair_plan", "dm_rs_repair_device_async", "dm_repair_buffer", "dm_repair_files",
     "dm_aes_cbc_encrypt_device_async", "dm_aes_cbc_decrypt_device_async", "dm_process_cipher_buffer",
-    "dm_restore_cipher_buffer",
+    "dm_restore_cipher_buffer", "dm_aes_cbc_encrypt_range_device_async", "dm_full_processing_cipher",
     "dm_range_plan", "dm_aes_cbc_decrypt_windows_device_async", "dm_restore_range_buffer", "dm_retrieve_range",
     "dm_pstream_open", "dm_pstream_write", "dm_pstream_close", "dm_pstream_abort",
     "dm_tree_node_count", "dm_tree_depth", "dm_tree_levels_device_async", "dm_tree_levels",
@@ -143,6 +143,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "dm_process_cipher_buffer": ([vp, vp, u64, u64, vp, u64, vp, vp, vp, vp], i32),
         "dm_restore_cipher_buffer": ([vp, pvp, vp, vp, vp, u64, u64, u64, i32, vp, u64, vp, vp, vp,
                                       ctypes.POINTER(i32)], i32),
+        "dm_aes_cbc_encrypt_range_device_async": ([vp, vp, u64, vp, vp, u64, u64, u64, u64, u64, vp], i32),
+        "dm_full_processing_cipher": ([vp, ctypes.c_char_p, ctypes.c_char_p, u64, vp, u64, i32, vp, vp, u64, pu64,
+                                       vp], i32),
         "dm_range_plan": ([u64, u64, u64, i32, i32, u64, u64, i32, pu64, pu64, vp, u64, vp, u64, pu64], i32),
         "dm_aes_cbc_decrypt_windows_device_async": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
         "dm_restore_range_buffer": ([vp, pvp, vp, u64, u64, u64, u64, u64, i32, vp, u64, vp, vp, vp,

@@ -21,6 +21,9 @@
 //       never leaves registers; the plaintext is loaded kAesDepth blocks ahead.  16 chains per
 //       wave, one wave per workgroup: 256 segments spread over 16 CUs' SIMDs.
 //       Latency-bound like the SHA-256 chains: a throughput path.
+//   aes_cbc_encrypt_range_kernel  the same chains, blocks [blk_lo, blk_hi) only: the chaining value
+//       is read back from the buffer, so the striped file path (fullproc_capi.inl) encrypts each
+//       stripe as it lands and the SHA-256 chains follow one stripe behind.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -137,6 +140,55 @@ void aes_cbc_encrypt_kernel(AesEncArgs a) {
             const uint32_t x = pf[i] ^ c;
             // block b + kAesDepth (still plaintext: the chain has written blocks < b only)
             pf[i] = b + kAesDepth < nblk ? p[4 * (b + kAesDepth)] : kAesPadWord;
+            c = aes_encrypt_quad<NR>(x, rk, tab);
+            p[4 * b] = c;
+        }
+    }
+}
+
+// The chain in pieces: plaintext blocks [blk_lo, blk_hi) of every chain, in place.  CBC resumes from
+// the previous ciphertext block alone, and that one is in the buffer (blk_lo - 1; the IV at 0), so
+// a launch carries no state to the next.  Blocks at or beyond blk_hi are neither read nor written
+// -- in the striped file path they are still on the copy stream -- but for the padding block, which
+// the launch that ends the data (blk_hi == nblk) appends.  Grid and layout as above.
+struct AesEncRangeArgs {
+    AesEncArgs e;
+    uint64_t blk_lo, blk_hi;   // blk_lo < blk_hi <= e.nblk
+};
+
+template <int NR>
+__global__ __launch_bounds__(kAesEncThreads)
+void aes_cbc_encrypt_range_kernel(AesEncRangeArgs ra) {
+    __shared__ uint32_t tab[5 * 256];
+    aes_fill_lds<kAesEncThreads>(tab, kAesTables.te0, kAesTables.sbox);
+    const AesEncArgs& a = ra.e;
+    const uint32_t j = threadIdx.x & 3u;
+    const uint64_t chain = ((uint64_t)blockIdx.x * kAesEncThreads + threadIdx.x) / kAesLanesPerChain;
+    if (chain >= a.nseg) return;
+    uint32_t rk[NR + 1];
+#pragma unroll
+    for (int r = 0; r <= NR; r++) {
+        const uint32_t k01 = j & 1u ? a.rk.w[4 * r + 1] : a.rk.w[4 * r];
+        const uint32_t k23 = j & 1u ? a.rk.w[4 * r + 3] : a.rk.w[4 * r + 2];
+        rk[r] = j & 2u ? k23 : k01;
+    }
+    uint32_t* p = reinterpret_cast<uint32_t*>(a.dev + chain * a.stride) + j;   // this lane's column of block 0
+    const uint64_t lo = ra.blk_lo, hi = ra.blk_hi;
+    const uint64_t end = hi == a.nblk ? hi + 1 : hi;   // the padding block comes after the last data block
+    const uint32_t iv01 = j & 1u ? a.iv[1] : a.iv[0], iv23 = j & 1u ? a.iv[3] : a.iv[2];
+    uint32_t c = j & 2u ? iv23 : iv01;
+    if (lo) c = p[4 * (lo - 1)];
+    uint32_t pf[kAesDepth];
+#pragma unroll
+    for (int i = 0; i < kAesDepth; i++) pf[i] = lo + i < hi ? p[4 * (lo + i)] : kAesPadWord;
+    for (uint64_t b0 = lo; b0 < end; b0 += kAesDepth) {
+#pragma unroll
+        for (int i = 0; i < kAesDepth; i++) {
+            const uint64_t b = b0 + i;
+            if (b >= end) break;
+            const uint32_t x = pf[i] ^ c;
+            // block b + kAesDepth (still plaintext: the chain has written blocks < b only); none at or past hi
+            pf[i] = b + kAesDepth < hi ? p[4 * (b + kAesDepth)] : kAesPadWord;
             c = aes_encrypt_quad<NR>(x, rk, tab);
             p[4 * b] = c;
         }

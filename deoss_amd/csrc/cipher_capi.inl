@@ -56,6 +56,26 @@ hipError_t launch_aes_encrypt(hipStream_t s, const CipherKey& k, uint8_t* dev, u
     return hipGetLastError();
 }
 
+// Blocks [blk_lo, blk_hi) of the same nseg chains (blk_lo < blk_hi <= plain / 16); the launch that
+// ends the data appends the padding block.
+hipError_t launch_aes_encrypt_range(hipStream_t s, const CipherKey& k, uint8_t* dev, uint64_t stride, uint64_t plain,
+                                    uint64_t nseg, uint64_t blk_lo, uint64_t blk_hi) {
+    dm::AesEncRangeArgs a{};
+    std::memcpy(a.e.rk.w, k.ks.enc, sizeof a.e.rk.w);
+    std::memcpy(a.e.iv, k.iv, 16);
+    a.e.dev = dev;
+    a.e.stride = stride;
+    a.e.nblk = plain / 16;
+    a.e.nseg = nseg;
+    a.blk_lo = blk_lo;
+    a.blk_hi = blk_hi;
+    const dim3 grid((uint32_t)ceil_div(nseg * dm::kAesLanesPerChain, dm::kAesEncThreads)), block(dm::kAesEncThreads);
+    aes_for_rounds(k.ks.rounds, [&](auto NR) {
+        hipLaunchKernelGGL(dm::aes_cbc_encrypt_range_kernel<decltype(NR)::value>, grid, block, 0, s, a);
+    });
+    return hipGetLastError();
+}
+
 // nseg x cipher_bytes of ciphertext -> nseg x (cipher_bytes - 16) of plaintext at out + t * out_stride,
 // pad_ok[t] = the padding block was sixteen 0x10 bytes.
 hipError_t launch_aes_decrypt(Dev& d, hipStream_t s, const CipherKey& k, const uint8_t* in, uint64_t in_stride,
@@ -155,6 +175,33 @@ int dm_aes_cbc_encrypt_device_async(dm_ctx* ctx, const void* key, uint64_t key_l
     hipStream_t s = pick_stream(d, stream);
     RC_TRY(begin_call(c, d, s));
     HIP_TRY(launch_aes_encrypt(s, k, static_cast<uint8_t*>(dev), stride, plain, nseg));
+    return DM_OK;
+}
+
+int dm_aes_cbc_encrypt_range_device_async(dm_ctx* ctx, const void* key, uint64_t key_len, const uint8_t iv[16],
+                                          void* dev, uint64_t stride, uint64_t plain, uint64_t nseg, uint64_t blk_lo,
+                                          uint64_t blk_hi, void* stream) {
+    if (!ctx || !key || !iv) return bad_arg();
+    const int g = device_of(ctx, dev);
+    CallLock lk(ctx, g, kReserved);
+    dm_ctx* c = ctx;
+    CipherKey k;
+    if (!dm_aes::expand_key(static_cast<const uint8_t*>(key), key_len, k.ks))
+        return fail(c, DM_ERR_INVALID, "%s", dm_cipher::kKeyLenError);
+    cipher_set_iv(k, iv);
+    if (nseg == 0) return DM_OK;
+    if (!dev || !is_aligned16(dev) || plain % 16 || stride % 16 || plain + 16 > stride)
+        return fail(c, DM_ERR_INVALID,
+                    "dm_aes_cbc_encrypt_range_device_async: need a 16-byte aligned buffer and stride, plain %% 16 == 0 "
+                    "and plain + 16 <= stride");
+    if (blk_lo >= blk_hi || blk_hi > plain / 16)
+        return fail(c, DM_ERR_INVALID,
+                    "dm_aes_cbc_encrypt_range_device_async: blocks [%llu, %llu) are not a range of the %llu of a chain",
+                    (unsigned long long)blk_lo, (unsigned long long)blk_hi, (unsigned long long)(plain / 16));
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    HIP_TRY(launch_aes_encrypt_range(s, k, static_cast<uint8_t*>(dev), stride, plain, nseg, blk_lo, blk_hi));
     return DM_OK;
 }
 

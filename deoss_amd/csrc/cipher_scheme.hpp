@@ -59,4 +59,23 @@ inline bool size_ok(uint64_t size, uint64_t nseg, uint64_t segment) {
     return nseg > 0 && size > (nseg - 1) * p && size <= nseg * p;
 }
 
+// The file path moves a window in stripes [o, o + w) of the ciphertext segment (o, w multiples of
+// 64, o + w <= segment).  On the way in a stripe is plaintext [off, off + len) of each piece, at the
+// same offset; the stripe that ends the segment carries 16 bytes less and the padding block, which
+// the encrypt kernel writes, is its last one.  w >= 64: never the padding block alone.
+struct StripeSpan {
+    uint64_t off = 0, len = 0;   // of the piece; both multiples of 16, len > 0
+    bool pad = false;            // the stripe ends in the padding block
+    uint64_t blk_lo() const { return off / kBlock; }
+    uint64_t blk_hi() const { return (off + len) / kBlock; }
+};
+inline StripeSpan stripe_span(uint64_t o, uint64_t w, uint64_t segment) {
+    const uint64_t piece = segment - kBlock, end = o + w < piece ? o + w : piece;
+    StripeSpan s;
+    s.off = o;
+    s.len = end - o;
+    s.pad = o + w == segment;
+    return s;
+}
+
 }  // namespace dm_cipher

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 namespace dm_fp {
 
@@ -100,6 +101,41 @@ struct FpSlots {
 inline FpSlots fp_slots(const FpLayout& L, uint64_t slot_bytes) {
     const uint64_t spd = std::max<uint64_t>(1, slot_bytes / L.seg), spp = std::max<uint64_t>(1, slot_bytes / L.pbytes);
     return {spd, spp, std::max(spd * L.seg, spp * L.pbytes)};
+}
+
+// Stripe schedule of the streamed paths (host buffers, files): W bytes of every leaf per step at
+// full width, but the stripes start at W/16 and grow by 1/8 per step.  The first stripe's transfer
+// overlaps nothing (the GPU waits for it), and each later one must finish within the previous
+// stripe's hashing (transfers run ~1.2x the chain-bound hash rate at 256 x 32 MiB).  Offsets and
+// widths are multiples of 64 (whole blocks).  Measured on the files path: 15.45 -> 15.70 GiB/s
+// (profiles/r02/LOGS.md#r02x_files.log).
+inline void stripe_schedule(uint64_t W, uint64_t len, std::vector<uint64_t>& so, std::vector<uint64_t>& sw) {
+    so.clear();
+    sw.clear();
+    for (uint64_t off = 0, w = std::max<uint64_t>(64, (W / 16) / 64 * 64); off < len;) {
+        so.push_back(off);
+        sw.push_back(w);
+        off += w;
+        w = std::min(W, std::max(w + 64, (w + w / 8) / 64 * 64));
+    }
+}
+
+// The striped FullProcessing pass over a window of ns segments: the slot's row pitch, and the
+// stripes [so[j], so[j] + sw[j]) of the segment -- stripe_schedule cut at the segment's end and at
+// every fragment boundary, so each stripe lies in one data fragment.  frag % 64 == 0.
+inline uint64_t fp_stripe_pitch(uint64_t slot_cap, uint64_t ns) { return std::max<uint64_t>(64, (slot_cap / ns) / 64 * 64); }
+inline void fp_stripe_plan(const FpLayout& L, uint64_t W, std::vector<uint64_t>& so, std::vector<uint64_t>& sw) {
+    std::vector<uint64_t> so0, sw0;
+    stripe_schedule(W, L.seg, so0, sw0);
+    so.clear();
+    sw.clear();
+    for (size_t j = 0; j < so0.size(); j++)
+        for (uint64_t o = so0[j], e = std::min(L.seg, so0[j] + sw0[j]); o < e;) {
+            const uint64_t b = std::min(e, (o / L.frag + 1) * L.frag);
+            so.push_back(o);
+            sw.push_back(b - o);
+            o = b;
+        }
 }
 
 }  // namespace dm_fp

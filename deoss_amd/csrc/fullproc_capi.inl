@@ -17,6 +17,13 @@
 // The fid is the hashtree root over all segment digests.  The Go shim's window path (read a
 // window, one batched GPU call, then write its fragments) leaves the GPU idle during the writes
 // and the writes idle during the hashing; here they overlap.
+//
+// dm_full_processing_cipher: the same with a cipher (cipher_scheme.hpp), through the same windows.
+// A segment is then the AES-CBC ciphertext of a P = segment - 16 byte piece of the file: the pieces
+// are read at the segment pitch and encrypted in place -- as whole chains, or with
+// DEOSS_FP_STRIPES=1 per stripe in the striped pass (the range kernel, with the SHA-256 chains one
+// stripe behind) -- and the data fragments and segment files, ciphertext, come back from HBM
+// through the slots as the parity does.
 
 namespace {
 
@@ -42,9 +49,11 @@ struct FpTrace {
 constexpr uint64_t kFpKeepBytes = 4ull << 30;   // window scratch kept between dm_full_processing calls
 
 struct FpEvents {
-    hipEvent_t slot[kFpSlots] = {}, rs = nullptr, copied = nullptr;
+    hipEvent_t slot[kFpSlots] = {}, enc[kFpSlots] = {}, rs = nullptr, copied = nullptr;
     ~FpEvents() {
         for (hipEvent_t e : slot)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : enc)
             if (e) (void)hipEventDestroy(e);
         if (rs) (void)hipEventDestroy(rs);
         if (copied) (void)hipEventDestroy(copied);
@@ -58,23 +67,22 @@ struct FpEvents {
 // the stripe lies in (kit->comp[1]).  After the last stripe: RS over the window and one leaf launch
 // over the parity fragments (on s), then the fid over the segment digests.  d.leaves: the striped
 // order (FpLayout::striped_frag_slot).
+// With a cipher (key) the window's pieces are fbeg + t * (seg - 16) of the file and a stripe brings
+// their plaintext [o, min(o + w, seg - 16)) (dm_cipher::stripe_span); after the stripe's copy one
+// range-encrypt launch on s -- idle until RS, which so follows the last encrypt -- makes it
+// ciphertext in place, and the two leaf launches wait for that instead of the copy.
 template <class TakeSlot>
 int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileSet& fs, uint64_t fbeg, uint64_t fend,
                     uint64_t ns, const FpLayout& L, uint64_t slot_cap, int readers, TakeSlot& take_slot,
-                    bool (&busy)[kFpSlots], FpEvents& ev, uint8_t* parity, uint8_t* dfid, FpTrace& tr) {
+                    bool (&busy)[kFpSlots], FpEvents& ev, uint8_t* parity, uint8_t* dfid, FpTrace& tr,
+                    const CipherKey* key) {
     dm_ctx* c = r->c;
     const int k = L.k, m = L.m;
     const uint64_t seg = L.seg, frag = L.frag;
-    const uint64_t W = std::max<uint64_t>(64, (slot_cap / ns) / 64 * 64);   // slot row pitch
-    std::vector<uint64_t> so0, sw0, so, sw;
-    stripe_schedule(W, seg, so0, sw0);
-    for (size_t j = 0; j < so0.size(); j++)   // no stripe crosses a fragment boundary
-        for (uint64_t o = so0[j], e = std::min(seg, so0[j] + sw0[j]); o < e;) {
-            const uint64_t b = std::min(e, (o / frag + 1) * frag);
-            so.push_back(o);
-            sw.push_back(b - o);
-            o = b;
-        }
+    const uint64_t pitch = key ? seg - dm_cipher::kBlock : seg;   // file bytes per segment
+    const uint64_t W = fp_stripe_pitch(slot_cap, ns);             // slot row pitch
+    std::vector<uint64_t> so, sw;
+    fp_stripe_plan(L, W, so, sw);   // no stripe crosses a fragment boundary
     const uint64_t nsteps = so.size();
     uint32_t* seg_state = reinterpret_cast<uint32_t*>(dfid + 256);
     uint32_t* frag_state = seg_state + 8 * ns;
@@ -99,17 +107,25 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
         int sl;
         RC_TRY(take_slot(&sl));
         uint8_t* buf = rs_ln(r, d).fp_slot[sl].u8();
+        const dm_cipher::StripeSpan sp = key ? dm_cipher::stripe_span(o, w, seg) : dm_cipher::StripeSpan{o, w, false};
         std::vector<FilePart> parts;
         for (uint64_t t = 0; t < ns; t++) {
-            const uint64_t a = fbeg + t * seg + o;
-            const uint64_t have = a < fend ? std::min(w, fend - a) : 0;
+            const uint64_t a = fbeg + t * pitch + o;
+            const uint64_t have = a < fend ? std::min(sp.len, fend - a) : 0;
             if (have) parts.push_back({0, a, have, buf + t * W});
-            if (have < w) std::memset(buf + t * W + have, 0, w - have);   // the last segment's zero padding
+            if (have < sp.len) std::memset(buf + t * W + have, 0, sp.len - have);   // the last segment's zero padding
         }
         RC_TRY(read_parts(c, fs, parts, readers));
-        HIP_TRY(hipMemcpy2DAsync(d.data.u8() + o, seg, buf, W, w, ns, hipMemcpyHostToDevice, d.copy));
+        HIP_TRY(hipMemcpy2DAsync(d.data.u8() + o, seg, buf, W, sp.len, ns, hipMemcpyHostToDevice, d.copy));
         HIP_TRY(hipEventRecord(ev.slot[sl], d.copy));
         busy[sl] = true;
+        hipEvent_t landed = ev.slot[sl];   // what the stripe's chains wait for
+        if (key) {
+            HIP_TRY(hipStreamWaitEvent(s, ev.slot[sl], 0));
+            HIP_TRY(launch_aes_encrypt_range(s, *key, d.data.u8(), seg, pitch, ns, sp.blk_lo(), sp.blk_hi()));
+            HIP_TRY(hipEventRecord(ev.enc[sl], s));
+            landed = ev.enc[sl];
+        }
         dm::LeafArgs la{};
         la.addrs = static_cast<const uint64_t*>(d.tab_addr.p) + j * ns;
         la.nleaves = ns;
@@ -118,14 +134,14 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
         la.state = seg_state;
         la.lens = static_cast<const uint64_t*>(d.tab_len.p);
         la.digests = d.leaves.u8();
-        HIP_TRY(hipStreamWaitEvent(kit->comp[0], ev.slot[sl], 0));
+        HIP_TRY(hipStreamWaitEvent(kit->comp[0], landed, 0));
         RC_TRY(launch_leaves(c, d, kit->comp[0], la, true, true, kind));
         la.byte_off = o - q * frag;
         la.byte_end = la.byte_off + w;
         la.state = frag_state;   // re-initialised where each fragment starts (byte_off 0)
         la.lens = static_cast<const uint64_t*>(d.tab_len.p) + ns;
         la.digests = d.leaves.u8() + 32 * L.striped_frag_slot(ns, 0, (int)q);
-        HIP_TRY(hipStreamWaitEvent(kit->comp[1], ev.slot[sl], 0));
+        HIP_TRY(hipStreamWaitEvent(kit->comp[1], landed, 0));
         RC_TRY(launch_leaves(c, d, kit->comp[1], la, true, true, kind));
     }
     tr.mark("A': stripes read, launched");
@@ -147,8 +163,11 @@ int fp_striped_pass(dm_rs* r, Dev& d, hipStream_t s, StreamKit* kit, const FileS
 }
 
 // Everything but the renames; `out` collects every file written under its temporary name.
+// key: null, or the cipher (cipher_scheme.hpp) -- segment t of the object is then the ciphertext of
+// the file's piece t, so every file written comes back from HBM, none from the file.
 int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out, uint64_t seg, int flags,
-                            std::vector<uint8_t>& segd, std::vector<uint8_t>& fragd, uint8_t fid[32]) {
+                            std::vector<uint8_t>& segd, std::vector<uint8_t>& fragd, uint8_t fid[32],
+                            const CipherKey* key) {
     dm_ctx* c = r->c;
     const int g = (int)(&d - c->devs.data());   // the call's lane
     RsLane& L = rs_ln(r, d);
@@ -156,7 +175,8 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
     const FpLayout lay(r->k, r->m, seg);
     const int total = lay.total;
     const uint64_t frag = lay.frag, pbytes = lay.pbytes;   // parity bytes per segment
-    const uint64_t size = fs.size[0], nseg = ceil_div(size, seg);
+    const uint64_t pitch = key ? seg - dm_cipher::kBlock : seg;   // file bytes per segment
+    const uint64_t size = fs.size[0], nseg = ceil_div(size, pitch);
     // test hooks (env, read per call): smaller slots / windows exercise slot reuse and multi-window fids
     const uint64_t window_bytes = env_bytes("DEOSS_FP_WINDOW_BYTES", kFpWindowBytes);
     const FpSlots slots = fp_slots(lay, env_bytes("DEOSS_FP_SLOT_BYTES", kFpSlotBytes));
@@ -167,13 +187,14 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
     for (auto& b : L.fp_slot) HIP_TRY(b.ensure(slot_cap));
     FpEvents ev;
     for (auto& e : ev.slot) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : ev.enc) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&ev.rs, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&ev.copied, hipEventDisableTiming));
     // where data files are copied from: the open file (kernel copies) or, for a pipe, its bytes
     const uint8_t* mem = fs.mem[0].empty() ? nullptr : fs.mem[0].data();
     int in_fd = fs.fd[0];
     FdGuard own_fd;
-    if (!mem && in_fd < 0) {
+    if (!key && !mem && in_fd < 0) {
         in_fd = own_fd.fd = ::open(fs.path[0].c_str(), O_RDONLY | O_CLOEXEC);
         if (in_fd < 0) return fail(c, DM_ERR_IO, "open %s: %s", fs.path[0].c_str(), go_errno(errno).c_str());
     }
@@ -208,6 +229,9 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
     const bool one_window = nseg <= win;
     const char* stripes_env = std::getenv("DEOSS_FP_STRIPES");
     const bool stripes_off = stripes_env != nullptr && stripes_env[0] == '0';
+    // with a cipher the default is the other way round: at 257 x 32 MiB the striped pass measured
+    // slower than encrypt-then-hash, so it runs only when DEOSS_FP_STRIPES asks for it
+    const bool stripes_want = key ? stripes_env != nullptr && !stripes_off : !stripes_off;
     // two extra compute streams for the striped pass (segment and data-fragment chains side by side)
     StreamKit* kit = nullptr;
     RC_TRY(kit_acquire(c, g, &kit));
@@ -223,12 +247,13 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
     FpTrace tr;
     for (uint64_t w0 = 0; w0 < nseg; w0 += win) {
         const uint64_t ns = std::min(win, nseg - w0);
-        const uint64_t fbeg = w0 * seg, fend = std::min(size, (w0 + ns) * seg);
+        const uint64_t fbeg = w0 * pitch, fend = std::min(size, (w0 + ns) * pitch);
         // striped (round 3): the window is read in stripes [o, o + w) of EVERY segment, so the segment
         // and data-fragment chains start with the first stripe instead of after the whole window
         // (the reads of an 8 GiB file took 236 ms before any chain started); needs whole 64-B blocks
-        // per fragment.  DEOSS_FP_STRIPES=0 keeps the read-then-launch order (A/B).
-        const bool striped = ns >= kFpStripeMinSegs && frag % 64 == 0 && !stripes_off;
+        // per fragment.  DEOSS_FP_STRIPES=0 keeps the read-then-launch order (A/B); with a cipher
+        // that order is the default and DEOSS_FP_STRIPES=1 asks for the stripes.
+        const bool striped = ns >= kFpStripeMinSegs && frag % 64 == 0 && stripes_want;
         HIP_TRY(d.data.ensure(ns * seg + kAlign));
         HIP_TRY(L.work.ensure(ns * pbytes + 256 + 2 * ns * 32));
         uint8_t* parity = L.work.u8();
@@ -236,7 +261,7 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
         if (!striped) {
             // A: file -> slots -> HBM, nothing else, so the leaf chains start as early as the reads allow
             for (uint64_t t0 = 0; t0 < ns; t0 += spd) {
-                const uint64_t nt = std::min(spd, ns - t0), len = nt * seg, a = fbeg + t0 * seg;
+                const uint64_t nt = std::min(spd, ns - t0), len = nt * pitch, a = fbeg + t0 * pitch;
                 int sl;
                 RC_TRY(take_slot(&sl));
                 uint8_t* buf = L.fp_slot[sl].u8();
@@ -246,10 +271,14 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
                     parts.push_back({0, a + q, std::min<uint64_t>(8ull << 20, have - q), buf + q});
                 RC_TRY(read_parts(c, fs, parts, readers));
                 if (have < len) std::memset(buf + have, 0, len - have);
-                HIP_TRY(hipMemcpyAsync(d.data.u8() + t0 * seg, buf, len, hipMemcpyHostToDevice, d.copy));
+                if (key)   // pieces at the segment pitch; the encrypt kernel appends each one's padding block
+                    HIP_TRY(hipMemcpy2DAsync(d.data.u8() + t0 * seg, seg, buf, pitch, pitch, nt, hipMemcpyHostToDevice,
+                                             d.copy));
+                else
+                    HIP_TRY(hipMemcpyAsync(d.data.u8() + t0 * seg, buf, len, hipMemcpyHostToDevice, d.copy));
                 HIP_TRY(hipEventRecord(ev.slot[sl], d.copy));
                 busy[sl] = true;
-                if (t0 + nt == ns && have < len) {   // the file's last, zero-padded segment: keep a copy
+                if (!key && t0 + nt == ns && have < len) {   // the file's last, zero-padded segment: keep a copy
                     tail.assign(buf + (nt - 1) * seg, buf + nt * seg);
                     tail_seg = w0 + t0 + nt - 1;
                 }
@@ -258,24 +287,41 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
             // B: RS + one leaf launch over segments and fragments, after the last H2D
             HIP_TRY(hipEventRecord(ev.copied, d.copy));
             HIP_TRY(hipStreamWaitEvent(s, ev.copied, 0));
+            if (key) HIP_TRY(launch_aes_encrypt(s, *key, d.data.u8(), seg, pitch, ns));
             RC_TRY(process_segments(r, d, s, d.data.u8(), seg, parity, {0, ns}, dfid, ev.rs));
         } else {
-            if (fend - fbeg < ns * seg) {   // the file's last, zero-padded segment, for its data files
+            if (!key && fend - fbeg < ns * seg) {   // the file's last, zero-padded segment, for its data files
                 tail.assign(seg, 0);
                 const uint64_t a = fbeg + (ns - 1) * seg;
                 RC_TRY(read_parts(c, fs, {{0, a, fend - a, tail.data()}}, readers));
                 tail_seg = w0 + ns - 1;
             }
             // the data files need only the file: their copies run from the start, beside the reads
-            start_data_files(w0, ns);
+            if (!key) start_data_files(w0, ns);
             RC_TRY(fp_striped_pass(r, d, s, kit, fs, fbeg, fend, ns, lay, slot_cap, readers, take_slot, busy, ev,
-                                   parity, dfid, tr));
+                                   parity, dfid, tr, key));
         }
         // C: while the leaf chains run, the parity comes back through the slots and is written as
         // each set lands (the data fragments and segment files are already being copied)
-        if (!striped) start_data_files(w0, ns);
+        if (!striped && !key) start_data_files(w0, ns);
         HIP_TRY(hipStreamWaitEvent(d.copy, ev.rs, 0));
         tr.mark("B: launched, data copies started");
+        // with a cipher the data fragments and segment files are ciphertext: they come back as the
+        // parity does, whole segments per slot, once RS -- which follows the last encrypt -- has run
+        for (uint64_t t0 = 0; key && t0 < ns; t0 += spd) {
+            const uint64_t nt = std::min(spd, ns - t0);
+            int sl;
+            RC_TRY(take_slot(&sl));
+            uint8_t* buf = L.fp_slot[sl].u8();
+            HIP_TRY(hipMemcpyAsync(buf, d.data.u8() + t0 * seg, nt * seg, hipMemcpyDeviceToHost, d.copy));
+            HIP_TRY(hipEventRecord(ev.slot[sl], d.copy));
+            HIP_TRY(hipEventSynchronize(ev.slot[sl]));
+            std::vector<FpFile> files;
+            for (uint64_t u = 0; u < nt; u++)
+                out.data_files(lay, w0 + t0 + u, buf + u * seg, -1, 0, (flags & DM_FP_SEGMENT_FILES) != 0, files);
+            wr[sl].start(std::move(files));
+            busy[sl] = true;
+        }
         for (uint64_t t0 = 0; t0 < ns; t0 += spp) {
             const uint64_t nt = std::min(spp, ns - t0);
             int sl;
@@ -318,23 +364,30 @@ int full_processing_windows(dm_rs* r, Dev& d, const FileSet& fs, FpOutputs& out,
     return DM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dm_full_processing(dm_rs* r, const char* path, const char* savedir, uint64_t segment, int flags,
-                       uint8_t* seg_hashes, uint8_t* frag_hashes, uint64_t cap, uint64_t* nseg_out, uint8_t fid[32]) {
+// dm_full_processing (cipher_len == 0) and dm_full_processing_cipher.
+int full_processing_call(dm_rs* r, const char* path, const char* savedir, uint64_t segment, const void* cipher,
+                         uint64_t cipher_len, int flags, uint8_t* seg_hashes, uint8_t* frag_hashes, uint64_t cap,
+                         uint64_t* nseg_out, uint8_t fid[32]) {
     if (!r || !path || !savedir || !fid) return bad_arg();
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
     if (nseg_out) *nseg_out = 0;
+    CipherKey ck;
+    const CipherKey* key = nullptr;
+    if (cipher_len) {
+        RC_TRY(cipher_key(c, cipher, cipher_len, ck));
+        key = &ck;
+    }
     FileSet fs;
     RC_TRY(open_files(c, &path, 1, fs));   // "open <path>: ..." first, as os.Open would fail
     const uint64_t size = fs.size[0];
     if (size == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
     RC_TRY(process_check(r, size, segment));
-    const uint64_t nseg = ceil_div(size, segment);
+    if (key && !dm_cipher::segment_ok(segment))
+        return fail(c, DM_ERR_INVALID, "segment size %llu has no room for a block and its padding block",
+                    (unsigned long long)segment);
+    const uint64_t nseg = key ? dm_cipher::geometry(size, segment).nseg : ceil_div(size, segment);
     if (nseg_out) *nseg_out = nseg;
     if ((seg_hashes || frag_hashes) && cap < nseg)
         return fail(c, DM_ERR_INVALID, "dm_full_processing: %llu segments, digest arrays hold %llu",
@@ -346,7 +399,7 @@ int dm_full_processing(dm_rs* r, const char* path, const char* savedir, uint64_t
     const int total = r->k + r->m;
     std::vector<uint8_t> segd(32 * nseg), fragd(32 * nseg * total);
     Dev& d = c->devs[g];
-    int rc = full_processing_windows(r, d, fs, out, segment, flags, segd, fragd, fid);
+    int rc = full_processing_windows(r, d, fs, out, segment, flags, segd, fragd, fid, key);
     {
         if (rc != DM_OK) {   // a failed call may leave copies queued: none may land in a slot the next call fills
             (void)hipStreamSynchronize(d.copy);
@@ -369,6 +422,22 @@ int dm_full_processing(dm_rs* r, const char* path, const char* savedir, uint64_t
     if (seg_hashes) std::memcpy(seg_hashes, segd.data(), segd.size());
     if (frag_hashes) std::memcpy(frag_hashes, fragd.data(), fragd.size());
     return DM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dm_full_processing(dm_rs* r, const char* path, const char* savedir, uint64_t segment, int flags,
+                       uint8_t* seg_hashes, uint8_t* frag_hashes, uint64_t cap, uint64_t* nseg_out, uint8_t fid[32]) {
+    return full_processing_call(r, path, savedir, segment, nullptr, 0, flags, seg_hashes, frag_hashes, cap, nseg_out, fid);
+}
+
+int dm_full_processing_cipher(dm_rs* r, const char* path, const char* savedir, uint64_t segment, const void* cipher,
+                              uint64_t cipher_len, int flags, uint8_t* seg_hashes, uint8_t* frag_hashes, uint64_t cap,
+                              uint64_t* nseg_out, uint8_t fid[32]) {
+    return full_processing_call(r, path, savedir, segment, cipher, cipher_len, flags, seg_hashes, frag_hashes, cap,
+                                nseg_out, fid);
 }
 
 }  // extern "C"

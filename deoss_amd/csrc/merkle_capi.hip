@@ -1112,22 +1112,7 @@ int pack_chunks(dm_ctx* c, Dev& d, const void* const* ptrs, const uint64_t* lens
     return h2d_at(c, d, ptrs, lens, n, off);
 }
 
-// Stripe schedule of the streamed paths (host buffers, files): W bytes of every leaf per step at
-// full width, but the stripes start at W/16 and grow by 1/8 per step.  The first stripe's transfer
-// overlaps nothing (the GPU waits for it), and each later one must finish within the previous
-// stripe's hashing (transfers run ~1.2x the chain-bound hash rate at 256 x 32 MiB).  Offsets and
-// widths are multiples of 64 (whole blocks).  Measured on the files path: 15.45 -> 15.70 GiB/s
-// (profiles/r02/LOGS.md#r02x_files.log).
-void stripe_schedule(uint64_t W, uint64_t len, std::vector<uint64_t>& so, std::vector<uint64_t>& sw) {
-    so.clear();
-    sw.clear();
-    for (uint64_t off = 0, w = std::max<uint64_t>(64, (W / 16) / 64 * 64); off < len;) {
-        so.push_back(off);
-        sw.push_back(w);
-        off += w;
-        w = std::min(W, std::max(w + 64, (w + w / 8) / 64 * 64));
-    }
-}
+// stripe_schedule, the stripe schedule of the streamed paths (host buffers, files): fp_layout.hpp.
 
 // Host object buffer -> HBM, hashing overlapped with the H2D copies.  Leaf digests land in
 // d.leaves; the caller reduces them.  Stripes: every leaf advances by W bytes per step, so all

@@ -235,6 +235,19 @@ class MerkleContext:
                                                             ctypes.c_void_p(stream or None)),
                     "dm_aes_cbc_encrypt_device_async")
 
+    def aes_cbc_encrypt_range_device_async(self, key: bytes, iv: bytes, dev_ptr: int, stride: int, plain: int,
+                                           nseg: int, blk_lo: int, blk_hi: int, stream: int = 0) -> None:
+        """``dm_aes_cbc_encrypt_range_device_async``: plaintext blocks [blk_lo, blk_hi) of the same
+        nseg chains, resumed from ciphertext block blk_lo - 1 in the buffer (the IV at 0); the call
+        with blk_hi == plain // 16 appends the PKCS#7 block.  Calls over consecutive ranges in
+        stream order equal one ``aes_cbc_encrypt_device_async``."""
+        if len(iv) != 16:
+            raise DeossMerkleError(DM_ERR_INVALID, "iv must be 16 bytes")
+        self._check(self._L.dm_aes_cbc_encrypt_range_device_async(self._h, bytes(key), len(key), bytes(iv),
+                                                                  ctypes.c_void_p(dev_ptr), stride, plain, nseg,
+                                                                  blk_lo, blk_hi, ctypes.c_void_p(stream or None)),
+                    "dm_aes_cbc_encrypt_range_device_async")
+
     def aes_cbc_decrypt_device_async(self, key: bytes, iv: bytes, dev_in: int, in_stride: int, cipher_bytes: int,
                                      nseg: int, dev_out: int, out_stride: int, dev_pad_ok: int,
                                      stream: int = 0) -> None:

@@ -20,8 +20,8 @@ Coding, hashing and the tree run on the GPU; there is no CPU fallback.  Segment 
 too (the zero-padded segment = its data fragments in order), so every returned path exists.
 :meth:`Processor.FullProcessing` is one ``dm_full_processing`` call: the library reads the file,
 and fragment writes overlap the reads and the GPU's hashing.
-With a non-empty ``cipher`` the object is AES-CBC encrypted on the GPU first (``dm_process_cipher_buffer``,
-window by window) and everything is named by ciphertext; :meth:`Processor.RestoreFile` with the
+With a non-empty ``cipher`` the object is AES-CBC encrypted on the GPU first (``dm_full_processing_cipher``,
+the same one call) and everything is named by ciphertext; :meth:`Processor.RestoreFile` with the
 same cipher gives the object back.  The scheme is recalled from the SDK, not pinned against it
 (DESIGN.md §6.14): parity-unpinned, and the Go shim still routes a cipher to the SDK.
 """
@@ -154,26 +154,31 @@ class Processor:
                                                         stream), "dm_process_device_async")
 
     # -- FullProcessing ----------------------------------------------------------------------------
-    def full_processing_file(self, file: str, savedir: str, segment_files: Optional[bool] = None
+    def full_processing_file(self, file: str, savedir: str, segment_files: Optional[bool] = None, cipher=b""
                              ) -> Tuple[bytes, bytes, bytes]:
         """One ``dm_full_processing`` call: the library reads ``file``, writes every fragment (and
-        segment) to ``savedir/<hex SHA-256>`` and returns (segment digests, fragment digests, fid)."""
+        segment) to ``savedir/<hex SHA-256>`` and returns (segment digests, fragment digests, fid).
+        With a ``cipher`` (16, 24 or 32 bytes) one ``dm_full_processing_cipher`` call: the same over
+        the ceil(size / (segment - 16)) segments of ciphertext."""
         L = self.ctx._L
+        key = _cipher_bytes(cipher)
+        piece = self.segment - CIPHER_BLOCK if key else self.segment
         if segment_files is None:
             segment_files = _write_segments()
         try:
             size = os.stat(file).st_size
         except OSError:
             size = 0
-        cap = max(1, (size + self.segment - 1) // self.segment)
+        cap = max(1, (size + piece - 1) // piece)
         total = self.k + self.m
         for _ in range(2):   # a FIFO / a file that grew: retry once with the count the library saw
             seg = ctypes.create_string_buffer(32 * cap)
             frag = ctypes.create_string_buffer(32 * cap * total)
             fid = ctypes.create_string_buffer(32)
             nseg = ctypes.c_uint64(0)
-            rc = L.dm_full_processing(self.enc._h, os.fsencode(file), os.fsencode(savedir), self.segment,
-                                      1 if segment_files else 0, seg, frag, cap, ctypes.byref(nseg), fid)
+            rc = L.dm_full_processing_cipher(self.enc._h, os.fsencode(file), os.fsencode(savedir), self.segment,
+                                             key, len(key), 1 if segment_files else 0, seg, frag, cap,
+                                             ctypes.byref(nseg), fid)
             if rc == DM_ERR_INVALID and nseg.value > cap:
                 cap = nseg.value
                 continue
@@ -494,12 +499,10 @@ class Processor:
     def FullProcessing(self, file: str, cipher: str, savedir: str
                        ) -> Tuple[Optional[List[SegmentDataInfo]], str, Optional[Exception]]:
         """FullProcessing in one library call (``dm_full_processing``: reads, coding, hashing and
-        fragment writes overlapped).  With a cipher: the window path (FullProcessingWindows), whose
-        every window is one ``dm_process_cipher_buffer`` call."""
-        if cipher:
-            return self.FullProcessingWindows(file, cipher, savedir)
+        fragment writes overlapped; with a cipher ``dm_full_processing_cipher``, the same windows
+        over AES-CBC ciphertext, every file written by the library)."""
         try:
-            segd, fragd, fid = self.full_processing_file(file, savedir)
+            segd, fragd, fid = self.full_processing_file(file, savedir, cipher=cipher)
         except (OSError, DeossMerkleError) as e:
             return None, "", e
         total = self.k + self.m

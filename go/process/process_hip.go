@@ -14,8 +14,10 @@
 //     fragment and segment file itself and overlaps those writes with the GPU's coding and hashing
 //     (one GPU pass per 32 GiB of file, no Go memory for the data);
 //   - cipher != "" (an encrypted upload, the Cipher header of node/objectHandler.go:102 and
-//     node/fileHandler.go:705): the SDK's own FullProcessing, unchanged -- its AES scheme is not
-//     restated here, so those uploads keep exactly the SDK's results.
+//     node/fileHandler.go:705): the SDK's own FullProcessing, unchanged, so those uploads keep
+//     exactly the SDK's results.  FullProcessingCipher does it on the GPU in one call
+//     (dm_full_processing_cipher) on a scheme recalled from the SDK, not yet confirmed against it;
+//     the routing changes in one line once it is (INTEGRATION.md "Encrypted uploads").
 // Swap it in by changing the handlers' import of github.com/CESSProject/cess-go-sdk/core/process to
 // this package (INTEGRATION.md).  Segment and fragment files are both written to savedir under
 // their hex SHA-256.  Build with `-tags hip`, CGO_ENABLED=1, PKG_CONFIG_PATH=<checkout>/deoss_amd.
@@ -305,11 +307,39 @@ func FullProcessingFiles(files []string, cipher string, savedir string) ([][]cha
 	return infos, fids, errs
 }
 
+// FullProcessingCipher (additive): FullProcessing(file, cipher, savedir) with a cipher on the GPU,
+// one dm_full_processing_cipher call on a pipeline lane -- the library reads the file in pieces of
+// chain.SegmentSize - 16 bytes, AES-CBC encrypts each into one segment as its stripes land, codes
+// and names the ciphertext and writes every file.  PARITY-UNPINNED: the scheme is recalled from the
+// SDK, not confirmed against it (INTEGRATION.md "Encrypted uploads"), so FullProcessing does not
+// route here: it still hands a cipher to the SDK.  An empty cipher is FullProcessing's large-file
+// path.
+func FullProcessingCipher(file string, cipher string, savedir string) ([]chain.SegmentDataInfo, string, error) {
+	if err := gpu(); err != nil {
+		return nil, "", err
+	}
+	piece := uint64(chain.SegmentSize)
+	if cipher != "" {
+		piece -= 16
+	}
+	nseg := uint64(1) // a missing or empty file: the library reports it in Go's words
+	if st, err := os.Stat(file); err == nil && st.Size() > 0 {
+		nseg = (uint64(st.Size()) + piece - 1) / piece
+	}
+	return fullProcessingOneCall(file, cipher, savedir, nseg)
+}
+
 // fullProcessingLarge: one dm_full_processing call on a free pipeline lane.  The library reads
 // the file, writes every fragment and segment file to savedir/<hex SHA-256> (data fragments while
 // the file is still being read, parity fragments while the leaf kernel hashes) and returns the
 // digests and the fid.
 func fullProcessingLarge(file, savedir string, nseg uint64) ([]chain.SegmentDataInfo, string, error) {
+	return fullProcessingOneCall(file, "", savedir, nseg)
+}
+
+// fullProcessingOneCall: dm_full_processing_cipher (with an empty cipher: dm_full_processing) on a
+// free pipeline lane; nseg sizes the digest arrays.
+func fullProcessingOneCall(file, cipher, savedir string, nseg uint64) ([]chain.SegmentDataInfo, string, error) {
 	total := uint64(chain.DataShards + chain.ParShards)
 	rs := <-pipes
 	defer func() { pipes <- rs }()
@@ -318,14 +348,15 @@ func fullProcessingLarge(file, savedir string, nseg uint64) ([]chain.SegmentData
 		fragd := make([]byte, 32*nseg*total)
 		var fid [32]byte
 		var got C.uint64_t
-		cfile, cdir := C.CString(file), C.CString(savedir)
+		cfile, cdir, ckey := C.CString(file), C.CString(savedir), C.CString(cipher)
 		flags := C.int(C.DM_FP_SEGMENT_FILES)
 		if !writeSegments {
 			flags = 0
 		}
 		runtime.LockOSThread() // dm_last_error is thread-local: call and read on one OS thread
-		rc := C.dm_full_processing(rs, cfile, cdir, C.uint64_t(chain.SegmentSize), flags,
-			(*C.uint8_t)(unsafe.Pointer(&segd[0])), (*C.uint8_t)(unsafe.Pointer(&fragd[0])), C.uint64_t(nseg), &got,
+		rc := C.dm_full_processing_cipher(rs, cfile, cdir, C.uint64_t(chain.SegmentSize),
+			unsafe.Pointer(ckey), C.uint64_t(len(cipher)), flags, (*C.uint8_t)(unsafe.Pointer(&segd[0])),
+			(*C.uint8_t)(unsafe.Pointer(&fragd[0])), C.uint64_t(nseg), &got,
 			(*C.uint8_t)(unsafe.Pointer(&fid[0])))
 		var err error
 		if rc != C.DM_OK {
@@ -338,6 +369,7 @@ func fullProcessingLarge(file, savedir string, nseg uint64) ([]chain.SegmentData
 		runtime.UnlockOSThread()
 		C.free(unsafe.Pointer(cfile))
 		C.free(unsafe.Pointer(cdir))
+		C.free(unsafe.Pointer(ckey))
 		if rc == C.DM_ERR_INVALID && uint64(got) > nseg && attempt == 0 { // the file grew since Stat
 			nseg = uint64(got)
 			continue

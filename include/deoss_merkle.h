@@ -397,6 +397,16 @@ int dm_repair_files(dm_rs *rs, const char *fragdir, const uint8_t *frag_names, u
  * path (many segments side by side). */
 int dm_aes_cbc_encrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16], void *dev,
                                     uint64_t stride, uint64_t plain, uint64_t nseg, void *stream);
+/* The same chains in pieces: plaintext blocks [blk_lo, blk_hi) of every segment, in place.  The
+ * chaining value is the IV when blk_lo == 0 and ciphertext block blk_lo - 1 of the buffer otherwise,
+ * so the calls for [0, a), [a, b), ... [z, plain / 16) in stream order give what one
+ * dm_aes_cbc_encrypt_device_async gives; the padding block is appended by the call with
+ * blk_hi == plain / 16 only, and no call reads or writes any other block at or beyond its blk_hi
+ * (those bytes may still be on their way in on another stream).  Checks as above, and
+ * blk_lo < blk_hi <= plain / 16 (else DM_ERR_INVALID, nothing runs). */
+int dm_aes_cbc_encrypt_range_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16],
+                                          void *dev, uint64_t stride, uint64_t plain, uint64_t nseg, uint64_t blk_lo,
+                                          uint64_t blk_hi, void *stream);
 /* Decrypt works out of place (the two buffers must not overlap): segment s's cipher_bytes at
  * dev_in + s*in_stride become cipher_bytes - 16 plaintext bytes at dev_out + s*out_stride (with
  * out_stride = cipher_bytes - 16 the output is the joined object), and dev_pad_ok[s] (one byte per
@@ -410,6 +420,19 @@ int dm_aes_cbc_decrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_l
 int dm_process_cipher_buffer(dm_rs *rs, const void *host, uint64_t len, uint64_t segment, const void *cipher,
                              uint64_t cipher_len, void *frags_out, uint8_t *seg_hashes, uint8_t *frag_hashes,
                              uint8_t fid[32]);
+/* dm_full_processing with a cipher: FullProcessing(file, cipher, savedir) from the file path in one
+ * call.  cipher_len == 0 is dm_full_processing; any other length but 16, 24 or 32 is DM_ERR_INVALID
+ * before savedir is touched.  The file's P-byte pieces are read at the segment pitch into a window
+ * (up to 32 GiB of segments), encrypted in place as whole chains, then coded and hashed as a plain
+ * window is.  With DEOSS_FP_STRIPES=1 a window of at least 4 segments is read in stripes instead,
+ * each stripe encrypted as it lands (one dm_aes_cbc_encrypt_range_device_async-style launch) with
+ * the SHA-256 chains of the segments and data fragments one stripe behind: faster at 8 and 64
+ * segments, slower at 257, hence not the default.  Every file --
+ * ciphertext -- comes back from the device through the pinned slots.  Outputs, flags, temporaries
+ * and error texts as dm_full_processing, over nseg = ceil(size / (segment - 16)). */
+int dm_full_processing_cipher(dm_rs *rs, const char *path, const char *savedir, uint64_t segment, const void *cipher,
+                              uint64_t cipher_len, int flags, uint8_t *seg_hashes, uint8_t *frag_hashes, uint64_t cap,
+                              uint64_t *nseg_out, uint8_t fid[32]);
 /* dm_restore_buffer with a cipher: the verified restore as there (every name and the fid are of
  * ciphertext), then every segment is decrypted and its padding block checked.  `size` is the
  * plaintext size, (nseg-1)*(segment-16) < size <= nseg*(segment-16).  A bad padding block -- what a

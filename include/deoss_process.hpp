@@ -4,7 +4,7 @@
 // node/tracker.go:767-769) and the streaming Writer (go/process/stream_hip.go), over the C ABI
 // (include/deoss_merkle.h: dm_full_processing, dm_pstream_*).  Same result shape: segment and
 // fragment path names under savedir (every one exists as a file), the hex fid, an error.
-// A non-empty cipher takes the window path over dm_process_cipher_buffer (the scheme is recalled
+// A non-empty cipher takes the same one call (dm_full_processing_cipher; the scheme is recalled
 // from the SDK, parity-unpinned: DESIGN.md §6.14; the Go shim still routes a cipher to the SDK).
 // Header-only; link -ldeoss_merkle.
 #pragma once
@@ -131,7 +131,8 @@ inline std::optional<Error> write_new(const std::string& path, const uint8_t* p,
     return std::nullopt;
 }
 
-// FullProcessing(file, cipher != "", savedir): the window path.  The file is read in windows of
+// FullProcessing(file, cipher != "", savedir) as it ran before dm_full_processing_cipher: the
+// window path, kept callable as the A/B baseline.  The file is read in windows of
 // WindowSegments pieces of segment - 16 plaintext bytes; each window is one
 // dm_process_cipher_buffer call (AES-CBC, coding and names on the GPU; segments are independent
 // chains, so windows carry no state), its fragment and segment files are written, and the fid is
@@ -191,10 +192,11 @@ inline Result FullProcessingCipher(const std::string& file, const std::string& c
 }
 
 // FullProcessing(file, cipher, savedir): one dm_full_processing call (the library reads the file
-// and writes every fragment and segment file to savedir/<hex SHA-256>); with a cipher, the window
-// path over dm_process_cipher_buffer (FullProcessingCipher).
-inline Result FullProcessing(const std::string& file, const std::string& cipher, const std::string& savedir) {
-    if (!cipher.empty()) return FullProcessingCipher(file, cipher, savedir);
+// and writes every fragment and segment file to savedir/<hex SHA-256>); with a cipher,
+// dm_full_processing_cipher, the same call over segments of ciphertext.  `segment` is
+// chain.SegmentSize outside tests.
+inline Result FullProcessing(const std::string& file, const std::string& cipher, const std::string& savedir,
+                             uint64_t segment = SegmentSize) {
     auto& p = Pipelines::instance();
     dm_rs* rs = p.pick();
     if (!rs) return {{}, "", Error{p.status(), dm_strerror(p.status())}};
@@ -204,8 +206,8 @@ inline Result FullProcessing(const std::string& file, const std::string& cipher,
         std::vector<uint8_t> segd(32 * cap), fragd(32 * cap * (DataShards + ParShards));
         uint8_t fid[32];
         uint64_t nseg = 0;
-        const int rc = dm_full_processing(rs, file.c_str(), savedir.c_str(), SegmentSize, flags, segd.data(),
-                                          fragd.data(), cap, &nseg, fid);
+        const int rc = dm_full_processing_cipher(rs, file.c_str(), savedir.c_str(), segment, cipher.data(), cipher.size(),
+                                                 flags, segd.data(), fragd.data(), cap, &nseg, fid);
         if (rc == DM_ERR_INVALID && nseg > cap) {
             cap = nseg;
             continue;
