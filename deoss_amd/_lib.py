@@ -37,6 +37,7 @@ EXPORTS = (
     "dm_timing_summary",
     "dm_rs_create", "dm_rs_destroy", "dm_rs_matrix", "dm_rs_encode", "dm_rs_encode_buffer", "dm_rs_reconstruct",
     "dm_rs_verify", "dm_rs_encode_device_async", "dm_rs_reconstruct_device_async",
+    "dm_rs_create_wide", "dm_rs_coding_matrix",
     "dm_process_device_async", "dm_process_buffer", "dm_process_batch", "dm_full_processing", "dm_fragment_lookup",
     "dm_rs_restore_plan", "dm_rs_restore_device_async", "dm_restore_buffer", "dm_retrieve_file",
     "dm_rs_repair_plan", "dm_rs_repair_device_async", "dm_repair_buffer", "dm_repair_files",
@@ -113,6 +114,8 @@ def _declare(L: ctypes.CDLL) -> None:
         "dm_timing_summary": ([vp, pu64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_double)], i32),
         "dm_rs_create": ([vp, i32, i32, ctypes.POINTER(vp)], i32),
+        "dm_rs_create_wide": ([vp, i32, i32, ctypes.POINTER(vp)], i32),
+        "dm_rs_coding_matrix": ([i32, i32, vp], i32),
         "dm_rs_destroy": ([vp], None),
         "dm_rs_matrix": ([vp, vp], i32),
         "dm_rs_encode": ([vp, pvp, pvp, u64], i32),

@@ -32,6 +32,7 @@ int dm_fragment_lookup(dm_rs* r, const char* path, uint64_t segment, const uint8
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_fragment_lookup"));
     FileSet fs;
     RC_TRY(open_files(c, &path, 1, fs));   // "open <path>: ..." as os.Open would fail
     const uint64_t size = fs.size[0];

@@ -373,6 +373,7 @@ int full_processing_call(dm_rs* r, const char* path, const char* savedir, uint64
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
     if (nseg_out) *nseg_out = 0;
+    RC_TRY(rs_narrow(r, cipher_len ? "dm_full_processing_cipher" : "dm_full_processing"));
     CipherKey ck;
     const CipherKey* key = nullptr;
     if (cipher_len) {

@@ -175,6 +175,7 @@ int dm_process_device_async(dm_rs* r, void* dev_obj, uint64_t len, uint64_t segm
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_process_device_async"));
     RC_TRY(process_check(r, len, segment));
     if (!dev_obj || !dev_parity || !dev_fid || !is_aligned16(dev_obj) || !is_aligned16(dev_parity))
         return fail(c, DM_ERR_INVALID, "dm_process_device_async: need 16-byte aligned object and parity buffers");
@@ -190,6 +191,7 @@ int dm_process_buffer(dm_rs* r, const void* host, uint64_t len, uint64_t segment
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_process_buffer"));
     if (!fid || (!host && len)) return fail(c, DM_ERR_INVALID, "dm_process_buffer: null argument");
     RC_TRY(process_check(r, len, segment));
     return process_host(r, c->devs[g], &host, &len, 1, segment, &frags_out, &seg_hashes, &frag_hashes, fid);
@@ -202,6 +204,7 @@ int dm_process_cipher_buffer(dm_rs* r, const void* host, uint64_t len, uint64_t 
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_process_cipher_buffer"));
     if (!fid || (!host && len)) return fail(c, DM_ERR_INVALID, "dm_process_cipher_buffer: null argument");
     RC_TRY(process_check(r, len, segment));
     if (!dm_cipher::segment_ok(segment))
@@ -222,6 +225,7 @@ int dm_process_batch(dm_rs* r, const void* const* objs, const uint64_t* lens, ui
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_process_batch"));
     if (nobj == 0) return DM_OK;
     if (!objs || !lens || !fids) return fail(c, DM_ERR_INVALID, "dm_process_batch: null argument");
     for (uint64_t o = 0; o < nobj; o++) {

@@ -344,6 +344,7 @@ int dm_pstream_open(dm_rs* r, uint64_t segment, const char* savedir, int flags, 
     dm_ctx* c = r->c;
     {
         CallLock lk(c, 0);
+        RC_TRY(rs_narrow(r, "dm_pstream_open"));
         RC_TRY(process_check(r, 1, segment));
     }
     DeviceRestore dev;

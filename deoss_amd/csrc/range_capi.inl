@@ -308,6 +308,7 @@ int dm_restore_range_buffer(dm_rs* r, const void* const* frags, const uint8_t* f
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_restore_range_buffer"));
     if (!frags || !out) return fail(c, DM_ERR_INVALID, "dm_restore_range_buffer: null argument");
     CipherKey key;
     const bool ciph = cipher != nullptr || cipher_len != 0;
@@ -349,6 +350,7 @@ int dm_retrieve_range(dm_rs* r, const char* fragdir, const uint8_t* frag_names, 
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_retrieve_range"));
     if (!fragdir || !frag_names || !out) return fail(c, DM_ERR_INVALID, "dm_retrieve_range: null argument");
     CipherKey key;
     const bool ciph = cipher != nullptr || cipher_len != 0;

@@ -454,6 +454,7 @@ int dm_rs_repair_device_async(dm_rs* r, void* const* dev_frags, const uint8_t* p
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_rs_repair_device_async"));
     const int k = r->k, total = r->k + r->m;
     if (!dev_frags || !present || nseg == 0 || frag == 0 || frag % 16)
         return fail(c, DM_ERR_INVALID,
@@ -480,6 +481,7 @@ int dm_repair_buffer(dm_rs* r, const void* const* frags, void* const* out, const
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_repair_buffer"));
     if (!frags || !out || !frag_names) return fail(c, DM_ERR_INVALID, "dm_repair_buffer: null argument");
     RC_TRY(repair_check(r, nseg, segment));
     Dev& d = c->devs[g];
@@ -508,6 +510,7 @@ int dm_repair_files(dm_rs* r, const char* fragdir, const uint8_t* frag_names, ui
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_repair_files"));
     if (!fragdir || !frag_names) return fail(c, DM_ERR_INVALID, "dm_repair_files: null argument");
     RC_TRY(repair_check(r, nseg, segment));
     std::string dir = fragdir;

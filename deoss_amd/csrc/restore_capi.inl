@@ -345,6 +345,7 @@ int restore_buffer_call(dm_rs* r, const char* fn, const void* const* frags, cons
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, fn));
     if (!frags || !out) return fail(c, DM_ERR_INVALID, "%s: null argument", fn);
     RC_TRY(restore_check(r, nseg, size, segment, key, cipher, cipher_len));
     RtStatus st(r, nseg);
@@ -392,6 +393,7 @@ int dm_rs_restore_device_async(dm_rs* r, const void* const* dev_frags, uint64_t 
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_rs_restore_device_async"));
     const int k = r->k, total = r->k + r->m;
     if (!dev_frags || !dev_obj || nseg == 0 || segment == 0 || segment % (16ull * (uint64_t)k) || !is_aligned16(dev_obj))
         return fail(c, DM_ERR_INVALID,
@@ -437,6 +439,7 @@ int dm_retrieve_file(dm_rs* r, const char* fragdir, const uint8_t* frag_names, c
     dm_ctx* c = r->c;
     const int g = rs_lane(c);
     CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_retrieve_file"));
     if (!fragdir || !frag_names || !out_path) return fail(c, DM_ERR_INVALID, "dm_retrieve_file: null argument");
     RC_TRY(restore_check(r, nseg, size, segment));
     std::string dir = fragdir;

@@ -3,7 +3,10 @@
 //
 // Mirrors github.com/klauspost/reedsolomon v1.12.4 (go.mod:65) as the cess-go-sdk uses it for
 // DeOSS fragments (New(chain.DataShards = 4, chain.ParShards = 8), node/tracker.go:250,369):
-//   New(data, parity)      -> dm_rs_create   (default Vandermonde-derived systematic matrix)
+//   New(data, parity)      -> dm_rs_create   (default Vandermonde-derived systematic matrix), up to 8 + 8:
+//                             the fragment coder every other dm_rs entry point takes;
+//                             dm_rs_create_wide: klauspost's whole range, data + parity <= 256, for the
+//                             calls listed here only (rs_code_wide_kernel beyond 8 + 8)
 //   Encode(shards)         -> dm_rs_encode / dm_rs_encode_device_async
 //   Reconstruct(shards)    -> dm_rs_reconstruct / dm_rs_reconstruct_device_async
 //   Verify(shards)         -> dm_rs_verify
@@ -11,6 +14,7 @@
 // The GF(2^8) arithmetic (rs_plan.hpp) only builds the small coding tables; all shard bytes are coded
 // by rs_code_kernel on the GPU (no CPU fallback).
 #include "rs_kernels.hpp"   // includes rs_plan.hpp: the host side of the coding (matrices, tables, plans)
+#include "rs_wide_kernels.hpp"
 
 using namespace dm_rsplan;
 
@@ -30,8 +34,9 @@ struct RsLane {
 struct dm_rs {
     dm_ctx* c = nullptr;
     int k = 0, m = 0;
+    bool wide = false;          // from dm_rs_create_wide beyond 8 + 8: rs_code_wide_kernel and its table layout
     std::vector<uint8_t> mat;   // (k + m) x k
-    DevBuf enc_tab;             // parity rows, k x 256 x 8 B (read-only after dm_rs_create)
+    DevBuf enc_tab;             // parity rows, k x 256 x 8 B; wide: ceil(m / 8) x k x 32 x 8 B (read-only after the create call)
     std::vector<RsLane> ln;     // one per call lane of the context's first GPU
 };
 
@@ -81,6 +86,23 @@ hipError_t launch_rs(Dev& d, hipStream_t s, int k, const dm::RsArgs& a) {
     return hipGetLastError();
 }
 
+// A wide coder's launch: rs_grid's x and y, one z layer per group of 8 outputs; nin x 256 B of LDS.
+hipError_t launch_rs_wide(Dev& d, hipStream_t s, const dm::RsWideArgs& a) {
+    dim3 grid = rs_grid(d, a.units_per_seg, a.nseg);
+    grid.z = (a.nout + kRsGroup - 1) / kRsGroup;
+    const size_t lds = (size_t)a.nin * kRsWideEntries * sizeof(uint2);
+    hipLaunchKernelGGL(dm::rs_code_wide_kernel, grid, dim3(dm::kRsThreads), lds, s, a);
+    return hipGetLastError();
+}
+
+// Every entry point outside the standalone coder's indexes kRsMaxIn / kRsMaxOut arrays by r->k and
+// r->m: a wide coder is refused there before anything is allocated, opened or launched.
+int rs_narrow(dm_rs* r, const char* fn) {
+    if (!r->wide) return DM_OK;
+    return fail(r->c, DM_ERR_INVALID, "%s needs a fragment coder of at most %d + %d shards", fn, dm::kRsMaxIn,
+                dm::kRsMaxOut);
+}
+
 // Encode arguments for nseg segments: data shard j of segment t at data + t * data_stride +
 // j * shard, parity shard i at parity + t * parity_stride + i * shard (r's parity rows).
 dm::RsArgs rs_encode_args(const dm_rs* r, const uint8_t* data, uint64_t data_stride, uint8_t* parity,
@@ -97,6 +119,24 @@ dm::RsArgs rs_encode_args(const dm_rs* r, const uint8_t* data, uint64_t data_str
     return a;
 }
 
+// Encode launch of either kind of coder, same layout as rs_encode_args.
+hipError_t launch_rs_encode(dm_rs* r, Dev& d, hipStream_t s, const uint8_t* data, uint64_t data_stride, uint8_t* parity,
+                            uint64_t parity_stride, uint64_t shard, uint64_t nseg) {
+    if (!r->wide) return launch_rs(d, s, r->k, rs_encode_args(r, data, data_stride, parity, parity_stride, shard, nseg));
+    dm::RsWideArgs a{};
+    a.in_base = data;
+    a.out_base = parity;
+    a.in_pitch = a.out_pitch = shard;
+    a.in_seg_stride = data_stride;
+    a.out_seg_stride = parity_stride;
+    a.units_per_seg = shard / 16;
+    a.nseg = nseg;
+    a.table = static_cast<const uint2*>(r->enc_tab.p);
+    a.nin = (uint32_t)r->k;
+    a.nout = (uint32_t)r->m;
+    return launch_rs_wide(d, s, a);
+}
+
 // What rs_pick_inputs and the plans built on it return (rs_plan.hpp), as the call's error.
 int plan_status(dm_ctx* c, int got, int k) {
     if (got == k) return DM_OK;
@@ -104,43 +144,41 @@ int plan_status(dm_ctx* c, int got, int k) {
     return fail(c, DM_ERR_INVALID, "too few shards given (%d of %d needed)", got, k);
 }
 
-// Coding rows that rebuild the missing shards from the first k present ones (klauspost
-// Reconstruct: the first `data` valid shards in index order; missing data rows come from the
-// inverse of their sub-matrix, missing parity rows = parity row x that inverse).
-int rs_decode_plan(dm_rs* r, const uint8_t* present, int* valid, int* missing, int* nmiss, std::vector<uint8_t>& rows) {
-    const int k = r->k, total = r->k + r->m;
-    *nmiss = 0;
-    for (int i = 0; i < total; i++)
-        if (!present[i]) missing[(*nmiss)++] = i;
-    uint8_t inv[dm::kRsMaxIn * dm::kRsMaxIn];
-    RC_TRY(plan_status(r->c, rs_pick_inputs(r->mat.data(), k, r->m, present, valid, inv), k));
-    const Gf& g = gf();
-    rows.assign((size_t)*nmiss * k, 0);
-    for (int t = 0; t < *nmiss; t++) {
-        const uint8_t* mrow = r->mat.data() + missing[t] * k;   // output = mrow x data = mrow x inv x valid
-        for (int j = 0; j < k; j++) {
-            uint8_t acc = 0;
-            for (int q = 0; q < k; q++) acc ^= g.mul(mrow[q], inv[q * k + j]);
-            rows[(size_t)t * k + j] = acc;
-        }
-    }
-    return DM_OK;
-}
-
+// Rebuilds the missing shards from the first k present ones (klauspost Reconstruct; the plan is
+// reconstruct_plan's, rs_plan.hpp) in one launch on s.
 int rs_reconstruct_dev(dm_rs* r, Dev& d, hipStream_t s, uint8_t* const* shards, const uint8_t* present,
                        uint64_t pitch, uint64_t nbytes_units) {
     dm_ctx* c = r->c;
-    int valid[dm::kRsMaxIn + dm::kRsMaxOut], missing[dm::kRsMaxIn + dm::kRsMaxOut], nmiss = 0;
-    std::vector<uint8_t> rows;
-    RC_TRY(rs_decode_plan(r, present, valid, missing, &nmiss, rows));
+    ReconstructPlan p;
+    RC_TRY(plan_status(c, reconstruct_plan(r->mat.data(), r->k, r->m, present, p), r->k));
+    const int nmiss = (int)p.outputs.size();
     if (nmiss == 0) return DM_OK;
-    const std::vector<uint64_t> tab = rs_table(rows.data(), nmiss, r->k);
-    RC_TRY(tables_begin(c, d, tab.size() * 8));
     RsLane& L = rs_ln(r, d);
+    if (r->wide) {
+        // the coding table, then the addresses of the k inputs and the nmiss outputs
+        std::vector<uint64_t> tab = rs_wide_table(p.rows.data(), nmiss, r->k);
+        const size_t ntab = tab.size();
+        for (int j = 0; j < r->k; j++) tab.push_back((uint64_t)reinterpret_cast<uintptr_t>(shards[p.inputs[j]]));
+        for (int t = 0; t < nmiss; t++) tab.push_back((uint64_t)reinterpret_cast<uintptr_t>(shards[p.outputs[t]]));
+        RC_TRY(tables_begin(c, d, tab.size() * 8));
+        RC_TRY(upload(c, d, s, L.dec_tab, tab.data(), tab.size() * 8));
+        dm::RsWideArgs a{};
+        a.addrs = static_cast<const uint64_t*>(L.dec_tab.p) + ntab;
+        a.in_seg_stride = a.out_seg_stride = pitch;
+        a.units_per_seg = nbytes_units;
+        a.nseg = 1;
+        a.table = static_cast<const uint2*>(L.dec_tab.p);
+        a.nin = (uint32_t)r->k;
+        a.nout = (uint32_t)nmiss;
+        HIP_TRY(launch_rs_wide(d, s, a));
+        return DM_OK;
+    }
+    const std::vector<uint64_t> tab = rs_table(p.rows.data(), nmiss, r->k);
+    RC_TRY(tables_begin(c, d, tab.size() * 8));
     RC_TRY(upload(c, d, s, L.dec_tab, tab.data(), tab.size() * 8));
     dm::RsArgs a{};
-    for (int j = 0; j < r->k; j++) a.in[j] = shards[valid[j]];
-    for (int t = 0; t < nmiss; t++) a.out[t] = shards[missing[t]];
+    for (int j = 0; j < r->k; j++) a.in[j] = shards[p.inputs[j]];
+    for (int t = 0; t < nmiss; t++) a.out[t] = shards[p.outputs[t]];
     a.in_seg_stride = a.out_seg_stride = pitch;
     a.units_per_seg = nbytes_units;
     a.nseg = 1;
@@ -150,29 +188,21 @@ int rs_reconstruct_dev(dm_rs* r, Dev& d, hipStream_t s, uint8_t* const* shards, 
     return DM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dm_rs_create(dm_ctx* ctx, int data_shards, int parity_shards, dm_rs** out) {
-    if (!ctx || !out) return bad_arg();
-    *out = nullptr;
-    CallLock lk(ctx, 0);
+// The coder of k + m shards on ctx's first GPU (counts checked by the caller, who holds the lock).
+int rs_create(dm_ctx* ctx, int k, int m, bool wide, dm_rs** out) {
     dm_ctx* c = ctx;
-    if (data_shards < 1 || data_shards > dm::kRsMaxIn || parity_shards < 1 || parity_shards > dm::kRsMaxOut)
-        return fail(c, DM_ERR_INVALID, "shard counts: 1 <= data <= %d, 1 <= parity <= %d", dm::kRsMaxIn,
-                    dm::kRsMaxOut);
     dm_rs* r = new (std::nothrow) dm_rs();
     if (!r) return fail(c, DM_ERR_NOMEM, "dm_rs_create: out of host memory");
     r->c = ctx;
-    r->k = data_shards;
-    r->m = parity_shards;
-    const int k = data_shards;
-    if (!rs_build_matrix(k, parity_shards, r->mat)) {
+    r->k = k;
+    r->m = m;
+    r->wide = wide;
+    if (!(wide ? rs_build_matrix_n(k, m, r->mat) : rs_build_matrix(k, m, r->mat))) {
         delete r;
         return fail(c, DM_ERR_INVALID, "singular Vandermonde top");
     }
-    const std::vector<uint64_t> tab = rs_table(r->mat.data() + (size_t)k * k, parity_shards, k);
+    const uint8_t* prows = r->mat.data() + (size_t)k * k;
+    const std::vector<uint64_t> tab = wide ? rs_wide_table(prows, m, k) : rs_table(prows, m, k);
     Dev& d = ctx->devs[0];
     r->ln.resize((size_t)ctx->lanes);
     r->enc_tab.rp = &ctx->reaper;
@@ -194,6 +224,52 @@ int dm_rs_create(dm_ctx* ctx, int data_shards, int parity_shards, dm_rs** out) {
         return fail(c, DM_ERR_HIP, "dm_rs_create: %s", hipGetErrorString(e));
     }
     *out = r;
+    return DM_OK;
+}
+
+// klauspost's New: ErrInvShardNum, ErrMaxShardNum (a coder without parity codes nothing here).
+int rs_wide_counts(dm_ctx* c, int data, int parity) {
+    if (data < 1)
+        return fail(c, DM_ERR_INVALID,
+                    "cannot create Encoder with less than one data shard or less than zero parity shards");
+    if (parity < 1) return fail(c, DM_ERR_INVALID, "cannot create Encoder with less than one parity shard");
+    if (data + parity > kRsWideMaxShards)
+        return fail(c, DM_ERR_INVALID, "cannot create Encoder with more than 256 data+parity shards");
+    return DM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dm_rs_create(dm_ctx* ctx, int data_shards, int parity_shards, dm_rs** out) {
+    if (!ctx || !out) return bad_arg();
+    *out = nullptr;
+    CallLock lk(ctx, 0);
+    dm_ctx* c = ctx;
+    if (data_shards < 1 || data_shards > dm::kRsMaxIn || parity_shards < 1 || parity_shards > dm::kRsMaxOut)
+        return fail(c, DM_ERR_INVALID, "shard counts: 1 <= data <= %d, 1 <= parity <= %d", dm::kRsMaxIn,
+                    dm::kRsMaxOut);
+    return rs_create(ctx, data_shards, parity_shards, false, out);
+}
+
+int dm_rs_create_wide(dm_ctx* ctx, int data_shards, int parity_shards, dm_rs** out) {
+    if (!ctx || !out) return bad_arg();
+    *out = nullptr;
+    CallLock lk(ctx, 0);
+    RC_TRY(rs_wide_counts(ctx, data_shards, parity_shards));
+    // DEOSS_RS_FORCE_WIDE (measurement only, tools/rs_wide_ab.py): the wide kernel within 8 + 8 too
+    static const bool force = std::getenv("DEOSS_RS_FORCE_WIDE") != nullptr;
+    const bool wide = data_shards > dm::kRsMaxIn || parity_shards > dm::kRsMaxOut || force;
+    return rs_create(ctx, data_shards, parity_shards, wide, out);
+}
+
+int dm_rs_coding_matrix(int data, int parity, uint8_t* out) {
+    if (!out) return bad_arg();
+    RC_TRY(rs_wide_counts(nullptr, data, parity));
+    std::vector<uint8_t> mat;
+    if (!rs_build_matrix_n(data, parity, mat)) return fail(nullptr, DM_ERR_INVALID, "singular Vandermonde top");
+    std::memcpy(out, mat.data(), mat.size());
     return DM_OK;
 }
 
@@ -233,11 +309,10 @@ int dm_rs_encode_device_async(dm_rs* r, const void* data, uint64_t data_stride, 
     Dev& d = c->devs[g];
     hipStream_t s = pick_stream(d, stream);
     RC_TRY(begin_call(c, d, s));
-    const dm::RsArgs a = rs_encode_args(r, static_cast<const uint8_t*>(data), data_stride, static_cast<uint8_t*>(parity),
-                                        parity_stride, shard, nseg);
     hipEvent_t* tr = timing_record(c, d);
     if (tr) HIP_TRY(hipEventRecord(tr[0], s));
-    HIP_TRY(launch_rs(d, s, r->k, a));
+    HIP_TRY(launch_rs_encode(r, d, s, static_cast<const uint8_t*>(data), data_stride, static_cast<uint8_t*>(parity),
+                             parity_stride, shard, nseg));
     if (tr) {
         HIP_TRY(hipEventRecord(tr[1], s));
         HIP_TRY(hipEventRecord(tr[2], s));
@@ -283,7 +358,7 @@ int dm_rs_encode(dm_rs* r, const void* const* data, void* const* parity, uint64_
     HIP_TRY(work.ensure(pitch * total));
     for (int j = 0; j < r->k; j++)
         HIP_TRY(hipMemcpyAsync(work.u8() + j * pitch, data[j], shard, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_rs(d, s, r->k, rs_encode_args(r, work.u8(), 0, work.u8() + r->k * pitch, 0, pitch, 1)));
+    HIP_TRY(launch_rs_encode(r, d, s, work.u8(), 0, work.u8() + r->k * pitch, 0, pitch, 1));
     for (int i = 0; i < r->m; i++)
         HIP_TRY(hipMemcpyAsync(parity[i], work.u8() + (r->k + i) * pitch, shard, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -3,11 +3,12 @@
 // restore's statuses, and the descriptors and tables of one restore or one repair launch.
 //
 // Shared by rs_capi.inl, restore_capi.inl, repair_capi.inl, rs_kernels.hpp (the shard limits and the
-// descriptor its kernels read) and the host tests (tests/cpp/test_rs_plan.cpp and
-// tests/cpp/test_repair_plan.cpp, plain and ASan/UBSan, no GPU).
+// descriptor its kernels read) and the host tests (tests/cpp/test_rs_plan.cpp,
+// tests/cpp/test_repair_plan.cpp and tests/cpp/test_rs_wide_plan.cpp, plain and ASan/UBSan, no GPU).
 // Mirrors klauspost/reedsolomon v1.12.4: its default matrix, and Reconstruct's choice of inputs.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -343,6 +344,127 @@ inline int repair_add(RepairBatch& b, uint8_t* const* frags, const uint8_t* pres
     if (p.nout > k) b.any_wide = true;
     b.desc.push_back(ds);
     return k;
+}
+
+// ---- any geometry up to 256 shards: the standalone coder (dm_rs_create_wide) --------------------
+// Heap-backed forms of the inverse, the matrix and the reconstruct plan for any k <= 255, and the
+// table layout of rs_code_wide_kernel.  Same arithmetic and pivoting as the fixed-size forms above,
+// so within 8 + 8 they give the same bytes.
+
+constexpr int kRsWideMaxShards = 256;   // klauspost: data + parity <= 256
+constexpr int kRsGroup = 8;             // outputs per table entry (one byte each)
+constexpr int kRsWideEntries = 32;      // table entries per input and group: 16 low-nibble, 16 high-nibble
+
+// Gauss-Jordan inverse of a k x k GF(2^8) matrix, any k; false if singular.
+inline bool gf_invert_n(const uint8_t* m, int k, std::vector<uint8_t>& out) {
+    const Gf& g = gf();
+    const size_t w2 = 2 * (size_t)k;
+    std::vector<uint8_t> w((size_t)k * w2, 0);
+    for (int r = 0; r < k; r++) {
+        std::memcpy(&w[r * w2], m + (size_t)r * k, (size_t)k);
+        w[r * w2 + k + r] = 1;
+    }
+    for (int c = 0; c < k; c++) {
+        int p = c;
+        while (p < k && w[p * w2 + c] == 0) p++;
+        if (p == k) return false;
+        if (p != c) std::swap_ranges(&w[p * w2], &w[p * w2] + w2, &w[c * w2]);
+        uint8_t* pc = &w[c * w2];
+        const uint8_t s = g.inv(pc[c]);
+        for (size_t j = 0; j < w2; j++) pc[j] = g.mul(pc[j], s);
+        for (int r = 0; r < k; r++) {
+            uint8_t* pr = &w[r * w2];
+            if (r == c || pr[c] == 0) continue;
+            const uint8_t f = pr[c];
+            for (size_t j = 0; j < w2; j++) pr[j] ^= g.mul(f, pc[j]);
+        }
+    }
+    out.resize((size_t)k * k);
+    for (int r = 0; r < k; r++) std::memcpy(&out[(size_t)r * k], &w[r * w2 + k], (size_t)k);
+    return true;
+}
+
+// rows (n x k) x b (k x k) -> out (n x k).
+inline void gf_matmul_n(const uint8_t* rows, int n, const uint8_t* b, int k, uint8_t* out) {
+    const Gf& g = gf();
+    for (int i = 0; i < n; i++) {
+        uint8_t* o = out + (size_t)i * k;
+        std::memset(o, 0, (size_t)k);
+        for (int t = 0; t < k; t++) {
+            const uint8_t f = rows[(size_t)i * k + t];
+            if (!f) continue;
+            const uint8_t* br = b + (size_t)t * k;
+            for (int j = 0; j < k; j++) o[j] ^= g.mul(f, br[j]);
+        }
+    }
+}
+
+// rs_build_matrix for 1 <= k, 1 <= m, k + m <= 256.
+inline bool rs_build_matrix_n(int k, int m, std::vector<uint8_t>& mat) {
+    const Gf& g = gf();
+    const int total = k + m;
+    std::vector<uint8_t> vm((size_t)total * k);
+    for (int i = 0; i < total; i++)
+        for (int j = 0; j < k; j++) vm[(size_t)i * k + j] = g.pow((uint8_t)i, j);
+    std::vector<uint8_t> inv;
+    if (!gf_invert_n(vm.data(), k, inv)) return false;
+    mat.assign((size_t)total * k, 0);
+    gf_matmul_n(vm.data(), total, inv.data(), k, mat.data());
+    return true;
+}
+
+struct ReconstructPlan {
+    std::vector<int> inputs;     // k: the first k present shards in index order
+    std::vector<int> outputs;    // every shard that is not present, in index order
+    std::vector<uint8_t> rows;   // outputs.size() x k
+};
+
+// klauspost's Reconstruct for one pattern (present[k + m]): a missing data shard gets its row of the
+// inverse of the inputs' sub-matrix, a missing parity shard (parity row) x that inverse.  Returns as
+// rs_pick_inputs; with nothing missing the plan has no outputs and nothing is inverted.
+inline int reconstruct_plan(const uint8_t* mat, int k, int m, const uint8_t* present, ReconstructPlan& p) {
+    const int total = k + m;
+    p.inputs.clear();
+    p.outputs.clear();
+    p.rows.clear();
+    int nv = 0;
+    for (int i = 0; i < total; i++) {
+        if (!present[i]) p.outputs.push_back(i);
+        else if (nv++ < k) p.inputs.push_back(i);
+    }
+    if (nv < k) return nv;
+    if (p.outputs.empty()) return k;
+    std::vector<uint8_t> sub((size_t)k * k), inv;
+    for (int i = 0; i < k; i++) std::memcpy(&sub[(size_t)i * k], mat + (size_t)p.inputs[i] * k, (size_t)k);
+    if (!gf_invert_n(sub.data(), k, inv)) return kPlanSingular;
+    p.rows.resize(p.outputs.size() * (size_t)k);
+    for (size_t t = 0; t < p.outputs.size(); t++) {
+        const int o = p.outputs[t];
+        uint8_t* row = &p.rows[t * (size_t)k];
+        if (o < k) std::memcpy(row, &inv[(size_t)o * k], (size_t)k);
+        else gf_matmul_n(mat + (size_t)o * k, 1, inv.data(), k, row);   // output = mrow x data = mrow x inv x inputs
+    }
+    return k;
+}
+
+// rs_code_wide_kernel's table of `rows` (nout x k, row-major): [ceil(nout / 8)][k][32] entries of
+// 8 B.  For output group g and input j, byte i of entry n < 16 is rows[8g + i][j] * n (the low
+// nibble's product) and of entry 16 + n is rows[8g + i][j] * (n << 4) (the high nibble's); a byte
+// past the last output is 0.  x * c = (x & 15) * c ^ (x & 0xf0) * c.
+inline std::vector<uint64_t> rs_wide_table(const uint8_t* rows, int nout, int k) {
+    const Gf& g = gf();
+    const int groups = (nout + kRsGroup - 1) / kRsGroup;
+    std::vector<uint64_t> t((size_t)groups * k * kRsWideEntries, 0);
+    for (int gr = 0; gr < groups; gr++)
+        for (int j = 0; j < k; j++)
+            for (int n = 0; n < kRsWideEntries; n++) {
+                const uint8_t x = n < 16 ? (uint8_t)n : (uint8_t)((n - 16) << 4);
+                uint64_t e = 0;
+                for (int i = 0; i < kRsGroup && gr * kRsGroup + i < nout; i++)
+                    e |= (uint64_t)g.mul(rows[(size_t)(gr * kRsGroup + i) * k + j], x) << (8 * i);
+                t[((size_t)gr * k + j) * kRsWideEntries + n] = e;
+            }
+    return t;
 }
 
 }  // namespace dm_rsplan

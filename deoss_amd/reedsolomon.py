@@ -6,8 +6,10 @@ cess-go-sdk (go.mod:8) codes every 32 MiB segment into ``chain.DataShards = 4`` 
 :func:`New` mirrors ``reedsolomon.New(dataShards, parityShards)``; the returned
 :class:`Encoder` has ``Split``, ``Encode``, ``Reconstruct`` and ``Verify`` with the same
 argument meaning (a list of shards, ``None`` / empty for a missing one) and the same errors
-(too few shards, short data).  Every byte is coded on the GPU (``rs_code_kernel``); there is no
-CPU fallback.  Device-resident forms take raw device pointers and a HIP stream handle.
+(too few shards, short data), over klauspost's whole range ``data + parity <= 256``.  Every byte is
+coded on the GPU (``rs_code_kernel``; beyond 8 + 8 ``rs_code_wide_kernel``); there is no CPU
+fallback.  Device-resident forms take raw device pointers and a HIP stream handle.  A coder
+beyond 8 + 8 is the standalone Encoder only: FullProcessing, restore and repair refuse it.
 """
 from __future__ import annotations
 
@@ -26,12 +28,13 @@ class ErrTooFewShards(DeossMerkleError):
 
 
 class Encoder:
-    def __init__(self, ctx: MerkleContext, data_shards: int, parity_shards: int):
+    def __init__(self, ctx: MerkleContext, data_shards: int, parity_shards: int, wide: bool = False):
         self._ctx = ctx
         self._L = ctx._L
         h = ctypes.c_void_p()
-        rc = self._L.dm_rs_create(ctx._h, data_shards, parity_shards, ctypes.byref(h))
-        ctx._check(rc, "dm_rs_create")
+        what = "dm_rs_create_wide" if wide else "dm_rs_create"
+        rc = getattr(self._L, what)(ctx._h, data_shards, parity_shards, ctypes.byref(h))
+        ctx._check(rc, what)
         self._h = h
         ctx._children.add(self)   # the context destroys this coder before itself
         self.data_shards = data_shards
@@ -230,5 +233,6 @@ def restore_plan(present: Sequence[bool], in_place: Optional[Sequence[bool]] = N
 
 
 def New(ctx: MerkleContext, data_shards: int = DATA_SHARDS, parity_shards: int = PAR_SHARDS) -> Encoder:
-    """reedsolomon.New(dataShards, parityShards) on the context's first GPU."""
-    return Encoder(ctx, data_shards, parity_shards)
+    """reedsolomon.New(dataShards, parityShards) on the context's first GPU: up to 8 + 8 the fragment
+    coder every path takes (``dm_rs_create``), beyond that the wide one (``dm_rs_create_wide``)."""
+    return Encoder(ctx, data_shards, parity_shards, wide=data_shards > 8 or parity_shards > 8)

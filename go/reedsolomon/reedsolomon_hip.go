@@ -4,9 +4,12 @@
 // github.com/klauspost/reedsolomon v1.12.4 (DeOSS go.mod:65) that cess-go-sdk uses to code each
 // segment into chain.DataShards + chain.ParShards fragments (node/tracker.go:250,369).  Same
 // constructor, method set and errors for New / Split / Encode / Reconstruct / Verify; the bytes
-// are coded by the MI355X library through include/deoss_merkle.h (dm_rs_*).  Only the default
-// matrix (no options) is provided.  Build with `-tags hip` and CGO_ENABLED=1; swap it in with a
-// go.mod `replace github.com/klauspost/reedsolomon => <this dir>` (INTEGRATION.md).
+// are coded by the MI355X library through include/deoss_merkle.h (dm_rs_*), over klauspost's whole
+// range dataShards + parityShards <= 256 (dm_rs_create_wide: within 8 + 8 the fragment coder the
+// FullProcessing paths use, beyond it the wide kernel).  Only the default matrix (no options) is
+// provided, and an Encoder without parity shards is ErrNotSupported.  Build with `-tags hip` and
+// CGO_ENABLED=1; swap it in with a go.mod `replace github.com/klauspost/reedsolomon => <this dir>`
+// (INTEGRATION.md).
 package reedsolomon
 
 /*
@@ -66,7 +69,7 @@ type rsGPU struct {
 	data, parity int
 }
 
-// New creates an Encoder for dataShards + parityShards (1..8 each on the GPU path).
+// New creates an Encoder for dataShards + parityShards (at least one of each, at most 256 in all).
 func New(dataShards, parityShards int, opts ...Option) (Encoder, error) {
 	if dataShards <= 0 || parityShards < 0 {
 		return nil, ErrInvShardNum
@@ -74,7 +77,7 @@ func New(dataShards, parityShards int, opts ...Option) (Encoder, error) {
 	if dataShards+parityShards > 256 {
 		return nil, ErrMaxShardNum
 	}
-	if dataShards > 8 || parityShards > 8 || parityShards == 0 {
+	if parityShards == 0 {
 		return nil, ErrNotSupported
 	}
 	c, err := gpu()
@@ -84,7 +87,7 @@ func New(dataShards, parityShards int, opts ...Option) (Encoder, error) {
 	r := &rsGPU{data: dataShards, parity: parityShards}
 	runtime.LockOSThread() // dm_last_error is thread-local: call and read on one OS thread
 	defer runtime.UnlockOSThread()
-	if rc := C.dm_rs_create(c, C.int(dataShards), C.int(parityShards), &r.h); rc != C.DM_OK {
+	if rc := C.dm_rs_create_wide(c, C.int(dataShards), C.int(parityShards), &r.h); rc != C.DM_OK {
 		return nil, errors.New(C.GoString(C.dm_last_error(c)))
 	}
 	runtime.SetFinalizer(r, func(x *rsGPU) { C.dm_rs_destroy(x.h) })

@@ -192,6 +192,19 @@ int dm_read_probe_async(dm_ctx *ctx, const void *dev, uint64_t nbytes, void *dev
 typedef struct dm_rs dm_rs;
 /* reedsolomon.New(data_shards, parity_shards): 1 <= data <= 8, 1 <= parity <= 8. */
 int dm_rs_create(dm_ctx *ctx, int data_shards, int parity_shards, dm_rs **out);
+/* reedsolomon.New over klauspost's whole range: 1 <= data, 1 <= parity, data + parity <= 256
+ * (else DM_ERR_INVALID with klauspost's text, "cannot create Encoder with more than 256 data+parity
+ * shards" / "... less than one data shard ...").  Within 8 + 8 the result is dm_rs_create's, usable
+ * everywhere.  A wider coder (rs_code_wide_kernel; the geometries stores use, 10 + 4, 12 + 4, 16 + 4,
+ * 17 + 3, ...) is the standalone Encoder only: dm_rs_destroy, dm_rs_matrix, dm_rs_encode,
+ * dm_rs_encode_buffer, dm_rs_reconstruct, dm_rs_verify, dm_rs_encode_device_async and
+ * dm_rs_reconstruct_device_async take it as they take any coder; every other call with a dm_rs
+ * argument (FullProcessing, restore, repair, ranged restore, pstreams) returns DM_ERR_INVALID
+ * "<call> needs a fragment coder of at most 8 + 8 shards" before it does anything. */
+int dm_rs_create_wide(dm_ctx *ctx, int data_shards, int parity_shards, dm_rs **out);
+/* The (data + parity) x data matrix every coder of that geometry uses, row-major (pure host
+ * function: no GPU, no context).  Counts as dm_rs_create_wide. */
+int dm_rs_coding_matrix(int data, int parity, uint8_t *out);
 void dm_rs_destroy(dm_rs *rs);
 /* The (data + parity) x data encoding matrix, row-major (top data rows = identity). */
 int dm_rs_matrix(dm_rs *rs, uint8_t *out);
