@@ -1,7 +1,7 @@
 // range_capi.inl -- ranged restore on the GPU: bytes [off, off + len) of an object from just the
 // fragments that cover them (dm_range_plan, dm_restore_range_buffer, dm_retrieve_range;
 // include/deoss_merkle.h).  Part of merkle_capi.hip (after repair_capi.inl; shares rt_hash, rt_load,
-// RtStatus, repair_launch and the pinned slots with the restore and repair paths).  The plan is
+// RtStatus, rs_desc_launch and the pinned slots with the restore and repair paths).  The plan is
 // range_plan.hpp, the window decryption aes_cbc_decrypt_window_kernel (cipher_capi.inl).
 //
 // Replaces, for the HTTP Range of GET /file/open (node/fileHandler.go:399-545), the whole-object
@@ -159,7 +159,7 @@ int range_run(RangeCall& q, uint64_t t0, uint64_t ns, const std::vector<uint8_t>
                 }
             RC_TRY(plan_status(c, repair_add(b, ptr, present), k));
         }
-        RC_TRY(repair_launch(r, d, s, b, frag / 16));
+        RC_TRY(rs_desc_launch(r, d, s, b, frag / 16));
         dig.clear();
         if (wnames && !outs.empty()) {
             std::vector<uint64_t> addrs;

@@ -1,8 +1,8 @@
 // repair_capi.inl -- the storage side on the GPU: a segment's lost fragments, data or parity, from
 // any `data` survivors (dm_rs_repair_*, dm_repair_buffer, dm_repair_files; include/deoss_merkle.h).
-// Part of merkle_capi.hip (after restore_capi.inl; shares rt_hash, rt_load, RtStatus and the pinned
-// slots with the restore path).  Plans and a launch's descriptors are rs_plan.hpp (repair_plan,
-// RepairBatch), the file writes are fp_files.hpp.
+// Part of merkle_capi.hip (after restore_capi.inl; shares rs_desc_launch, rt_hash, rt_load, RtStatus
+// and the pinned slots with the restore path).  Plans and a launch's descriptors are rs_plan.hpp
+// (repair_plan, repair_add), the file writes are fp_files.hpp.
 //
 // Replaces, for a fragment that went missing, DeOSS's reFullProcessing (node/tracker.go:320-355,
 // checkFileState): that one re-reads the object, needs the client's cipher and rewrites all 12
@@ -20,29 +20,6 @@ namespace {
 
 constexpr uint64_t kRepairWindowBytes = 16ull << 30;  // dm_repair_files: loaded + rebuilt fragment bytes per GPU pass (a pass costs one 8 MiB chain, 122 ms, however few fragments it holds)
 constexpr uint8_t kFragRebuilt = 4;                   // frag_status beyond the restore path's (rs_plan.hpp)
-
-int repair_launch(dm_rs* r, Dev& d, hipStream_t s, const RepairBatch& b, uint64_t units) {
-    dm_ctx* c = r->c;
-    if (!b.any_out) return DM_OK;
-    RsLane& L = rs_ln(r, d);
-    const uint64_t dbytes = b.desc.size() * sizeof(dm::RsRestoreDesc), tbytes = b.tabs.size() * 8;
-    RC_TRY(tables_begin(c, d, dbytes + tbytes + 1024));
-    RC_TRY(upload(c, d, s, L.rst_desc, b.desc.data(), dbytes));
-    RC_TRY(upload(c, d, s, L.rst_tab, b.tabs.data(), tbytes));
-    dm::RsRestoreArgs a{};
-    a.desc = static_cast<const dm::RsRestoreDesc*>(L.rst_desc.p);
-    a.tables = static_cast<const uint2*>(L.rst_tab.p);
-    a.units_per_seg = units;
-    a.nseg = b.desc.size();
-    const dim3 grid = rs_grid(d, units, a.nseg), block(dm::kRsThreads);
-    // what the batch shows: with at most k outputs everywhere the narrower restore kernel does it
-    if (b.any_wide)
-        rs_for_k(r->k, [&](auto K) { hipLaunchKernelGGL(dm::rs_repair_kernel<decltype(K)::value>, grid, block, 0, s, a); });
-    else
-        rs_for_k(r->k, [&](auto K) { hipLaunchKernelGGL(dm::rs_restore_kernel<decltype(K)::value>, grid, block, 0, s, a); });
-    HIP_TRY(hipGetLastError());
-    return DM_OK;
-}
 
 // Where a run of segments' fragments come from and where the rebuilt ones go (indices are
 // t * total + j within the run).
@@ -164,7 +141,7 @@ int repair_rounds(dm_rs* r, Dev& d, hipStream_t s, RepairIo& io, uint64_t ns, ui
         RC_TRY(io.load(loads));
         hipEvent_t* tr = timing_record(c, d);   // one record per round: one repair and one leaf launch
         if (tr) HIP_TRY(hipEventRecord(tr[0], s));
-        RC_TRY(repair_launch(r, d, s, b, frag / 16));
+        RC_TRY(rs_desc_launch(r, d, s, b, frag / 16));
         std::vector<uint64_t> addrs;
         for (const RtLoad& l : loads) addrs.push_back(reinterpret_cast<uint64_t>(l.to));
         for (const Seg& sg : segs)
@@ -439,7 +416,7 @@ int dm_rs_repair_plan(int data, int parity, const uint8_t* present, const uint8_
             return fail(nullptr, DM_ERR_INVALID, "singular Vandermonde top");
         mat = cached;
     }
-    RepairPlan p;
+    RsPlan p;
     RC_TRY(plan_status(nullptr, repair_plan(mat.data(), data, parity, present, want, p), data));
     std::memcpy(inputs, p.inputs, sizeof(int) * (size_t)data);
     std::memcpy(outputs, p.outputs, sizeof(int) * (size_t)p.nout);
@@ -471,7 +448,7 @@ int dm_rs_repair_device_async(dm_rs* r, void* const* dev_frags, const uint8_t* p
     Dev& d = c->devs[g];
     hipStream_t s = pick_stream(d, stream);
     RC_TRY(begin_call(c, d, s));
-    return repair_launch(r, d, s, b, frag / 16);
+    return rs_desc_launch(r, d, s, b, frag / 16);
 }
 
 int dm_repair_buffer(dm_rs* r, const void* const* frags, void* const* out, const uint8_t* frag_names, uint64_t nseg,

@@ -24,7 +24,7 @@ namespace {
 constexpr uint64_t kRtWindowBytes = 1ull << 30;   // dm_retrieve_file: segment bytes per GPU pass (+ 2x parity scratch)
 constexpr int kRtReaders = 8;                      // fragment files read at once into a pinned slot
 
-int restore_launch(dm_rs* r, Dev& d, hipStream_t s, const RestoreBatch& b, uint64_t units) {
+int rs_desc_launch(dm_rs* r, Dev& d, hipStream_t s, const RsBatch& b, uint64_t units) {
     dm_ctx* c = r->c;
     if (!b.any_out) return DM_OK;
     RsLane& L = rs_ln(r, d);
@@ -32,13 +32,13 @@ int restore_launch(dm_rs* r, Dev& d, hipStream_t s, const RestoreBatch& b, uint6
     RC_TRY(tables_begin(c, d, dbytes + tbytes + 1024));
     RC_TRY(upload(c, d, s, L.rst_desc, b.desc.data(), dbytes));
     RC_TRY(upload(c, d, s, L.rst_tab, b.tabs.data(), tbytes));
-    dm::RsRestoreArgs a{};
-    a.desc = static_cast<const dm::RsRestoreDesc*>(L.rst_desc.p);
-    a.tables = static_cast<const uint2*>(L.rst_tab.p);
-    a.units_per_seg = units;
-    a.nseg = b.desc.size();
+    const dm::RsRestoreArgs a{static_cast<const dm::RsRestoreDesc*>(L.rst_desc.p), static_cast<const uint2*>(L.rst_tab.p),
+                              units, b.desc.size()};
     const dim3 grid = rs_grid(d, units, a.nseg), block(dm::kRsThreads);
-    rs_for_k(r->k, [&](auto K) { hipLaunchKernelGGL(dm::rs_restore_kernel<decltype(K)::value>, grid, block, 0, s, a); });
+    if (b.any_wide)   // a repair with more than k outputs somewhere; else the narrower kernel does it
+        rs_for_k(r->k, [&](auto K) { hipLaunchKernelGGL(dm::rs_repair_kernel<decltype(K)::value>, grid, block, 0, s, a); });
+    else
+        rs_for_k(r->k, [&](auto K) { hipLaunchKernelGGL(dm::rs_restore_kernel<decltype(K)::value>, grid, block, 0, s, a); });
     HIP_TRY(hipGetLastError());
     return DM_OK;
 }
@@ -105,7 +105,7 @@ int rt_rebuild(dm_rs* r, Dev& d, hipStream_t s, const RtFrags& f, uint64_t ns, u
     RestoreBatch b{r->mat.data(), k, r->m};
     for (uint64_t t = 0; t < ns; t++)
         RC_TRY(plan_status(c, restore_add(b, f.data() + t * total, base + t * segment, frag), k));
-    RC_TRY(restore_launch(r, d, s, b, frag / 16));
+    RC_TRY(rs_desc_launch(r, d, s, b, frag / 16));
     res = Rebuild::kDone;
     if (!seg_names && !want_segd) return DM_OK;
     std::vector<uint64_t> sa(ns);
@@ -378,7 +378,7 @@ int dm_rs_restore_plan(int data, int parity, const uint8_t* present, const uint8
             return fail(nullptr, DM_ERR_INVALID, "singular Vandermonde top");
         mat = cached;
     }
-    RestorePlan p;
+    RsPlan p;
     RC_TRY(plan_status(nullptr, restore_plan(mat.data(), data, parity, present, in_place, p), data));
     std::memcpy(inputs, p.inputs, sizeof(int) * (size_t)data);
     std::memcpy(outputs, p.outputs, sizeof(int) * (size_t)p.nout);
@@ -412,7 +412,7 @@ int dm_rs_restore_device_async(dm_rs* r, const void* const* dev_frags, uint64_t 
     Dev& d = c->devs[g];
     hipStream_t s = pick_stream(d, stream);
     RC_TRY(begin_call(c, d, s));
-    return restore_launch(r, d, s, b, frag / 16);
+    return rs_desc_launch(r, d, s, b, frag / 16);
 }
 
 int dm_restore_buffer(dm_rs* r, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,

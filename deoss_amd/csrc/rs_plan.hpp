@@ -138,19 +138,22 @@ inline int rs_pick_inputs(const uint8_t* mat, int k, int m, const uint8_t* prese
     return gf_invert(sub, k, inv) ? k : kPlanSingular;
 }
 
-struct RestorePlan {
+static_assert(kRsMaxOut <= kRsMaxIn, "RsRestoreDesc::out holds a repair's outputs");
+
+// What restore_plan and repair_plan make of one pattern.
+struct RsPlan {
     int inputs[kRsMaxIn];
-    int outputs[kRsMaxIn];
+    int outputs[kRsMaxOut];
     int nout = 0;
-    uint8_t rows[kRsMaxIn * kRsMaxIn];   // nout x k
+    uint8_t rows[kRsMaxOut * kRsMaxIn];   // nout x k
 };
+typedef RsPlan RestorePlan, RepairPlan;   // the names the two sides had before they shared the type
 
 // The plan of one pattern: every data fragment that is missing or not at its final address is
 // written, fragment j with row j of the inverse of the inputs' sub-matrix (a unit row when j is
 // itself an input: a present data fragment always is).  in_place is nullable (nothing in place).
 // Returns as rs_pick_inputs.
-inline int restore_plan(const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* in_place,
-                        RestorePlan& p) {
+inline int restore_plan(const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* in_place, RsPlan& p) {
     uint8_t inv[kRsMaxIn * kRsMaxIn];
     const int got = rs_pick_inputs(mat, k, m, present, p.inputs, inv);
     if (got != k) return got;
@@ -188,82 +191,11 @@ inline bool rt_select(int k, int total, uint64_t ns, const uint8_t* const* good,
     return all;
 }
 
-// Descriptors and coding tables of one restore launch, built segment by segment; mat is the coder's
-// (k + m) x k matrix and outlives the batch.
-struct RestoreBatch {
-    struct Cached {
-        RestorePlan p;
-        uint32_t tab;
-    };
-    const uint8_t* mat;
-    int k, m;
-    std::vector<dm::RsRestoreDesc> desc;
-    std::vector<uint64_t> tabs;                 // [ntab][k][256]
-    std::map<uint32_t, Cached> plans;           // present mask | in-place mask << 16
-    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index (one table per distinct plan)
-    bool any_out = false;
-};
-
-// Segment whose usable fragments are frags[0 .. total) (device addresses, NULL = absent; never
-// dereferenced here) and whose data fragment j belongs at seg_base + j * frag.  Returns as
-// rs_pick_inputs.
-inline int restore_add(RestoreBatch& b, const uint8_t* const* frags, uint8_t* seg_base, uint64_t frag) {
-    const int k = b.k, total = b.k + b.m;
-    uint8_t present[kRsMaxIn + kRsMaxOut], in_place[kRsMaxIn];
-    uint32_t key = 0;
-    for (int j = 0; j < total; j++) {
-        present[j] = frags[j] != nullptr;
-        key |= (uint32_t)present[j] << j;
-        if (j < k) {
-            in_place[j] = frags[j] == seg_base + (uint64_t)j * frag;
-            key |= (uint32_t)in_place[j] << (16 + j);
-        }
-    }
-    auto it = b.plans.find(key);
-    if (it == b.plans.end()) {
-        RestoreBatch::Cached cp;
-        const int got = restore_plan(b.mat, k, b.m, present, in_place, cp.p);
-        if (got != k) return got;
-        cp.tab = 0;
-        if (cp.p.nout) {
-            const std::string rows(reinterpret_cast<const char*>(cp.p.rows), (size_t)cp.p.nout * k);
-            auto t = b.tab_of.find(rows);
-            if (t == b.tab_of.end()) {
-                const std::vector<uint64_t> tab = rs_table(cp.p.rows, cp.p.nout, k);
-                t = b.tab_of.emplace(rows, (uint32_t)(b.tabs.size() / ((size_t)k * 256))).first;
-                b.tabs.insert(b.tabs.end(), tab.begin(), tab.end());
-            }
-            cp.tab = t->second;
-        }
-        it = b.plans.emplace(key, cp).first;
-    }
-    const RestorePlan& p = it->second.p;
-    dm::RsRestoreDesc ds{};
-    for (int j = 0; j < k; j++) ds.in[j] = frags[p.inputs[j]];
-    for (int i = 0; i < p.nout; i++) ds.out[i] = seg_base + (uint64_t)p.outputs[i] * frag;
-    ds.nout = (uint32_t)p.nout;
-    ds.table = it->second.tab;
-    if (p.nout) b.any_out = true;
-    b.desc.push_back(ds);
-    return k;
-}
-
-// ---- repair: the missing fragments of a segment, data or parity, from the survivors -------------
-
-static_assert(kRsMaxOut <= kRsMaxIn, "RsRestoreDesc::out holds a repair's outputs");
-
-struct RepairPlan {
-    int inputs[kRsMaxIn];
-    int outputs[kRsMaxOut];
-    int nout = 0;
-    uint8_t rows[kRsMaxOut * kRsMaxIn];   // nout x k
-};
-
-// The plan of one pattern: every fragment j with want[j] && !present[j] is written (want nullable:
-// every missing one), a data fragment with row j of the inverse of the inputs' sub-matrix, a parity
-// fragment with mat[j] x that inverse.  At most m <= kRsMaxOut fragments are missing once k are
-// present.  Returns as rs_pick_inputs.
-inline int repair_plan(const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* want, RepairPlan& p) {
+// The plan of one pattern for a repair: every fragment j with want[j] && !present[j] is written (want
+// nullable: every missing one), a data fragment with row j of the inverse of the inputs' sub-matrix,
+// a parity fragment with mat[j] x that inverse.  A present fragment is never written.  At most
+// m <= kRsMaxOut fragments are missing once k are present.  Returns as rs_pick_inputs.
+inline int repair_plan(const uint8_t* mat, int k, int m, const uint8_t* present, const uint8_t* want, RsPlan& p) {
     uint8_t inv[kRsMaxIn * kRsMaxIn];
     const int got = rs_pick_inputs(mat, k, m, present, p.inputs, inv);
     if (got != k) return got;
@@ -287,39 +219,34 @@ inline int repair_plan(const uint8_t* mat, int k, int m, const uint8_t* present,
     return k;
 }
 
-// Descriptors and coding tables of one repair launch, built segment by segment (RestoreBatch's
-// counterpart; the descriptor and the table layout are the restore kernel's).
-struct RepairBatch {
+// Descriptors and coding tables of one restore or one repair launch, built segment by segment; mat
+// is the coder's (k + m) x k matrix and outlives the batch.
+struct RsBatch {
     struct Cached {
-        RepairPlan p;
+        RsPlan p;
         uint32_t tab;
     };
     const uint8_t* mat;
     int k, m;
     std::vector<dm::RsRestoreDesc> desc;
     std::vector<uint64_t> tabs;                 // [ntab][k][256]
-    std::map<uint32_t, Cached> plans;           // present mask | want mask << 16
-    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index
+    std::map<uint32_t, Cached> plans;           // present mask | in-place (restore) or want (repair) mask << 16
+    std::map<std::string, uint32_t> tab_of;     // coding rows -> table index (one table per distinct plan)
     bool any_out = false;
-    bool any_wide = false;                      // some segment has nout > k: the restore kernel cannot run it
+    bool any_wide = false;                      // some segment has nout > k (repair only): rs_restore_kernel cannot run it
 };
+typedef RsBatch RestoreBatch, RepairBatch;
 
-// Segment whose fragment j lies, or is to be written, at frags[j] (device addresses, never
-// dereferenced here): present[j] != 0 holds the fragment; present[j] == 0 and frags[j] != NULL is
-// wanted; NULL is absent and not wanted.  Returns as rs_pick_inputs.
-inline int repair_add(RepairBatch& b, uint8_t* const* frags, const uint8_t* present) {
-    const int k = b.k, total = b.k + b.m;
-    uint8_t pres[kRsMaxIn + kRsMaxOut], want[kRsMaxIn + kRsMaxOut];
-    uint32_t key = 0;
-    for (int j = 0; j < total; j++) {
-        pres[j] = present[j] != 0 && frags[j] != nullptr;
-        want[j] = !pres[j] && frags[j] != nullptr;
-        key |= (uint32_t)pres[j] << j | (uint32_t)want[j] << (16 + j);
-    }
+// What restore_add and repair_add share once a segment's key is known: its plan (cached by key, else
+// from plan(RsPlan&), which returns as rs_pick_inputs), the plan's table (shared by coding rows), and
+// the descriptor, whose inputs are frags[plan input] and whose output i lies at out_at(fragment index).
+template <class PlanFn, class OutFn>
+inline int batch_add(RsBatch& b, uint32_t key, const uint8_t* const* frags, PlanFn plan, OutFn out_at) {
+    const int k = b.k;
     auto it = b.plans.find(key);
     if (it == b.plans.end()) {
-        RepairBatch::Cached cp;
-        const int got = repair_plan(b.mat, k, b.m, pres, want, cp.p);
+        RsBatch::Cached cp;
+        const int got = plan(cp.p);
         if (got != k) return got;
         cp.tab = 0;
         if (cp.p.nout) {
@@ -334,16 +261,51 @@ inline int repair_add(RepairBatch& b, uint8_t* const* frags, const uint8_t* pres
         }
         it = b.plans.emplace(key, cp).first;
     }
-    const RepairPlan& p = it->second.p;
+    const RsPlan& p = it->second.p;
     dm::RsRestoreDesc ds{};
     for (int j = 0; j < k; j++) ds.in[j] = frags[p.inputs[j]];
-    for (int i = 0; i < p.nout; i++) ds.out[i] = frags[p.outputs[i]];
+    for (int i = 0; i < p.nout; i++) ds.out[i] = out_at(p.outputs[i]);
     ds.nout = (uint32_t)p.nout;
     ds.table = it->second.tab;
     if (p.nout) b.any_out = true;
     if (p.nout > k) b.any_wide = true;
     b.desc.push_back(ds);
     return k;
+}
+
+// Segment whose usable fragments are frags[0 .. total) (device addresses, NULL = absent; never
+// dereferenced here) and whose data fragment j belongs at seg_base + j * frag.  Returns as
+// rs_pick_inputs.
+inline int restore_add(RestoreBatch& b, const uint8_t* const* frags, uint8_t* seg_base, uint64_t frag) {
+    const int k = b.k, total = b.k + b.m;
+    uint8_t present[kRsMaxIn + kRsMaxOut], in_place[kRsMaxIn];
+    uint32_t key = 0;
+    for (int j = 0; j < total; j++) {
+        present[j] = frags[j] != nullptr;
+        key |= (uint32_t)present[j] << j;
+        if (j < k) {
+            in_place[j] = frags[j] == seg_base + (uint64_t)j * frag;
+            key |= (uint32_t)in_place[j] << (16 + j);
+        }
+    }
+    return batch_add(b, key, frags, [&](RsPlan& p) { return restore_plan(b.mat, k, b.m, present, in_place, p); },
+                     [&](int j) { return seg_base + (uint64_t)j * frag; });
+}
+
+// Segment whose fragment j lies, or is to be written, at frags[j] (device addresses, never
+// dereferenced here): present[j] != 0 holds the fragment; present[j] == 0 and frags[j] != NULL is
+// wanted; NULL is absent and not wanted.  Returns as rs_pick_inputs.
+inline int repair_add(RepairBatch& b, uint8_t* const* frags, const uint8_t* present) {
+    const int total = b.k + b.m;
+    uint8_t pres[kRsMaxIn + kRsMaxOut], want[kRsMaxIn + kRsMaxOut];
+    uint32_t key = 0;
+    for (int j = 0; j < total; j++) {
+        pres[j] = present[j] != 0 && frags[j] != nullptr;
+        want[j] = !pres[j] && frags[j] != nullptr;
+        key |= (uint32_t)pres[j] << j | (uint32_t)want[j] << (16 + j);
+    }
+    return batch_add(b, key, frags, [&](RsPlan& p) { return repair_plan(b.mat, b.k, b.m, pres, want, p); },
+                     [&](int j) { return frags[j]; });
 }
 
 // ---- any geometry up to 256 shards: the standalone coder (dm_rs_create_wide) --------------------

@@ -6,7 +6,7 @@
 // outputs go in groups of 8: as in rs_code_kernel one 8-byte table entry carries a byte's
 // contribution to 8 outputs at the same position, a lane owns 16 consecutive positions and keeps
 // their 16 accumulators in registers, and the position-major accumulators become shard-major words
-// by 4x4 byte transposes.  What differs:
+// by rs_kernels.hpp's rs_shard_words.  What differs from its rs_code_units:
 //   - the inputs are walked by a run-time loop (one 16-B load in flight while the previous input is
 //     looked up), so every output group reads all nin inputs again: per segment nin * ceil(nout/8)
 //     shard reads and nout shard writes, no read-modify-write of partial outputs;
@@ -112,11 +112,7 @@ void rs_code_wide_kernel(RsWideArgs a) {
                 }
                 // output o0 + i, word q = byte i of acc[4q .. 4q+3]
                 uint32_t lo[4][4], hi[4][4];   // [q][row]
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    transpose4(acc[4 * q].x, acc[4 * q + 1].x, acc[4 * q + 2].x, acc[4 * q + 3].x, lo[q]);
-                    transpose4(acc[4 * q].y, acc[4 * q + 1].y, acc[4 * q + 2].y, acc[4 * q + 3].y, hi[q]);
-                }
+                rs_shard_words<true>(acc, lo, hi);
 #pragma unroll
                 for (int i = 0; i < 4; i++)
                     if (i < (int)no)

@@ -166,6 +166,46 @@ def test_kernel_want_subsets(ctx, oracle_lib):
     assert not tgt.any()
 
 
+def _mixed_missing(rng, k, counts):
+    """Per count n the held fragments of a k + 8 segment that misses n, data and parity mixed (a
+    single missing one is either)."""
+    pats = []
+    for n in counts:
+        nd = rng.randint(max(1, n - 8), min(k, n - 1)) if n >= 2 else rng.randint(0, min(n, 1))
+        gone = set(rng.sample(range(k), nd)) | set(rng.sample(range(k, k + 8), n - nd))
+        pats.append(sorted(set(range(k + 8)) - gone))
+    return pats
+
+
+@pytest.mark.parametrize("k,call", [(k, "restore_kernel") for k in range(1, 9)] +
+                         [(k, "repair_kernel") for k in range(1, 8)])
+def test_kernel_every_instance(ctx, oracle_lib, k, call):
+    """Every rs_restore_kernel<k> and rs_repair_kernel<k>, k + 8, at 257 units per fragment: two
+    workgroups in x, the second with one live lane, so the prefetch guard and the loop bound are at
+    their edge.  Seven segments, one of them complete (nout 0).
+    restore_kernel: 1 .. k missing everywhere, so no segment has more outputs than inputs and
+    rs_restore_kernel<k> runs; one segment has nout == k, the last store its bound lets through, and
+    from k = 5 on segments on both sides of nout > 4 (with and without the entries' high half).
+    repair_kernel: one segment missing k + 1 and one missing 8 next to segments missing 1 .. 4, so
+    rs_repair_kernel<k> runs and takes both sides of its nout > 4 branch in one launch.  There is
+    no such case for k = 8: of 8 + 8 fragments at most 8 can be missing, never more than k, so
+    rs_repair_kernel<8> is unreachable."""
+    rng = random.Random(800 + k)
+    if call == "restore_kernel":
+        counts = [k, 1, max(1, k // 2), min(k, 4), max(1, k - 1), 0, min(k, 3)]
+    else:
+        counts = [1, k + 1, 3, 0, 8, 2, 4]
+    tgt = _device_repair(ctx, oracle_lib, k, 8, 16 * 257, _mixed_missing(rng, k, counts), None, 30 + k)
+    nout = tgt.sum(axis=1).tolist()
+    assert nout == counts
+    assert tgt[:, :k].any() and tgt[:, k:].any()
+    if call == "restore_kernel":
+        assert max(nout) == k and min(nout) == 0
+        assert k < 5 or (max(nout) > 4 and any(0 < n <= 4 for n in nout))
+    else:
+        assert k + 1 in nout and 8 in nout and any(0 < n <= 4 for n in nout)
+
+
 def test_device_repair_too_few_fails_before_any_launch(ctx):
     torch = _torch()
     from deoss_amd import DeossMerkleError
