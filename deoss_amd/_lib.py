@@ -44,6 +44,7 @@ EXPORTS = (
     "dm_aes_cbc_encrypt_device_async", "dm_aes_cbc_decrypt_device_async", "dm_process_cipher_buffer",
     "dm_restore_cipher_buffer", "dm_aes_cbc_encrypt_range_device_async", "dm_full_processing_cipher",
     "dm_range_plan", "dm_aes_cbc_decrypt_windows_device_async", "dm_restore_range_buffer", "dm_retrieve_range",
+    "dm_aes_cbc_encrypt_keyed_device_async", "dm_process_cipher_batch", "dm_batcher_process_cipher",
     "dm_pstream_open", "dm_pstream_write", "dm_pstream_close", "dm_pstream_abort",
     "dm_tree_node_count", "dm_tree_depth", "dm_tree_levels_device_async", "dm_tree_levels",
     "dm_merkle_paths_device_async", "dm_merkle_paths", "dm_verify_paths_device_async", "dm_verify_paths",
@@ -64,6 +65,16 @@ class AesWindow(ctypes.Structure):
     """dm_aes_window: one window of a CBC chain on the device."""
     _fields_ = [("inp", ctypes.c_void_p), ("prev", ctypes.c_void_p), ("out", ctypes.c_void_p),
                 ("nblk", ctypes.c_uint64), ("check_pad", ctypes.c_int)]
+
+
+class AesKey(ctypes.Structure):
+    """dm_aes_key: one key of a keyed encryption (16, 24 or 32 bytes) and its IV."""
+    _fields_ = [("key", ctypes.c_void_p), ("key_len", ctypes.c_uint64), ("iv", ctypes.c_uint8 * 16)]
+
+
+class AesChain(ctypes.Structure):
+    """dm_aes_chain: one chain of a keyed encryption on the device and the index of its key."""
+    _fields_ = [("dev", ctypes.c_void_p), ("key_index", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class DeossMerkleError(RuntimeError):
@@ -151,6 +162,9 @@ def _declare(L: ctypes.CDLL) -> None:
                                        vp], i32),
         "dm_range_plan": ([u64, u64, u64, i32, i32, u64, u64, i32, pu64, pu64, vp, u64, vp, u64, pu64], i32),
         "dm_aes_cbc_decrypt_windows_device_async": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
+        "dm_aes_cbc_encrypt_keyed_device_async": ([vp, vp, u64, vp, u64, u64, vp], i32),
+        "dm_process_cipher_batch": ([vp, pvp, pu64, pvp, pu64, u64, u64, pvp, pvp, pvp, vp], i32),
+        "dm_batcher_process_cipher": ([vp, vp, u64, vp, u64, vp, vp, vp, vp], i32),
         "dm_restore_range_buffer": ([vp, pvp, vp, u64, u64, u64, u64, u64, i32, vp, u64, vp, vp, vp,
                                      ctypes.POINTER(i32)], i32),
         "dm_retrieve_range": ([vp, ctypes.c_char_p, vp, u64, u64, u64, u64, u64, i32, vp, u64, vp, vp, vp,

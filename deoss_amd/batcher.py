@@ -78,17 +78,25 @@ class Batcher:
         self._check(self._L.dm_batcher_root(self._h, src, n, leaves, root), "dm_batcher_root")
         return (leaves.raw[:32 * nl] if leaves is not None else None), root.raw
 
-    def process(self, buf, want_frags: bool = False) -> Tuple[bytes, bytes, bytes, Optional[bytes]]:
+    def process(self, buf, want_frags: bool = False, cipher=b"") -> Tuple[bytes, bytes, bytes, Optional[bytes]]:
         """FullProcessing of one object through the batcher: (segment digests, fragment digests,
-        fid, fragments or None)."""
+        fid, fragments or None).  With a ``cipher`` (16, 24 or 32 bytes) ``dm_batcher_process_cipher``:
+        the same over the ceil(len / (unit - 16)) segments of ciphertext; plain and encrypted
+        requests share batches."""
         src, n, _keep = self._src(buf)
-        nseg = (n + self.unit - 1) // self.unit
+        key = cipher.encode() if isinstance(cipher, str) else bytes(cipher or b"")
+        piece = self.unit - 16 if key else self.unit
+        nseg = (n + piece - 1) // piece
         total = self.k + self.m
         seg = ctypes.create_string_buffer(max(32 * nseg, 32))
         frag = ctypes.create_string_buffer(max(32 * nseg * total, 32))
         fid = ctypes.create_string_buffer(32)
         frags = ctypes.create_string_buffer(nseg * total * (self.unit // self.k)) if (want_frags and nseg) else None
-        self._check(self._L.dm_batcher_process(self._h, src, n, frags, seg, frag, fid), "dm_batcher_process")
+        if key:
+            self._check(self._L.dm_batcher_process_cipher(self._h, src, n, key, len(key), frags, seg, frag, fid),
+                        "dm_batcher_process_cipher")
+        else:
+            self._check(self._L.dm_batcher_process(self._h, src, n, frags, seg, frag, fid), "dm_batcher_process")
         return seg.raw[:32 * nseg], frag.raw[:32 * nseg * total], fid.raw, (frags.raw if frags is not None else None)
 
     def stats(self) -> Tuple[int, int, int]:

@@ -24,6 +24,10 @@
 //   aes_cbc_encrypt_range_kernel  the same chains, blocks [blk_lo, blk_hi) only: the chaining value
 //       is read back from the buffer, so the striped file path (fullproc_capi.inl) encrypts each
 //       stripe as it lands and the SHA-256 chains follow one stripe behind.
+//   aes_cbc_encrypt_keyed_kernel  the same chains with a key per chain: chains and keys come from
+//       tables in device memory, a wave holds chains of one round count (aes_keyed_plan.hpp) and
+//       branches once into the loop unrolled for it, so ONE launch encrypts a batch of different
+//       clients' uploads (dm_process_cipher_batch, the batcher) in the time of its longest chain.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -320,6 +324,82 @@ void aes_cbc_decrypt_window_kernel(AesWinArgs a) {
                 a.pad_ok[w] = (x.x == kAesPadWord && x.y == kAesPadWord && x.z == kAesPadWord && x.w == kAesPadWord) ? 1 : 0;
         }
     }
+}
+
+// ---- a key per chain: encrypted uploads of different clients in ONE launch (dm_process_cipher_batch) ----
+
+// One chain of a keyed launch: nblk plaintext blocks at dev, overwritten by nblk + 1 ciphertext
+// blocks under key table entry `key`.  dev == nullptr: an empty slot (aes_keyed_plan.hpp pads a
+// round-count group to whole waves with them).
+struct AesChainSlot {
+    uint8_t* dev;
+    uint32_t key;
+    uint32_t pad_;
+};
+static_assert(sizeof(AesChainSlot) == 16, "one 16-byte descriptor per slot");
+
+// One key of a keyed launch: the encryption round keys (round-major column words, as AesKey) and
+// the IV.  The only place round keys sit in device memory: the host zeroes the table in stream
+// order right after the launch (launch_aes_encrypt_keyed).
+struct AesKeyEntry {
+    uint32_t w[dm_aes::kMaxKeyWords];
+    uint32_t iv[4];
+};
+static_assert(sizeof(AesKeyEntry) == 256, "60 round-key words + 4 IV words");
+
+struct AesKeyedArgs {
+    const AesChainSlot* slot;      // [16 * nwave], device memory
+    const AesKeyEntry* keys;       // device memory
+    const uint32_t* wave_rounds;   // [nwave]: 10, 12 or 14, the round count of every chain of the wave
+    uint64_t nblk;                 // plaintext blocks of every chain
+};
+
+// The chain of aes_cbc_encrypt_kernel with the key read from the table: lane j loads its column
+// w[4 r + j] of every round key and its IV word once, into registers.
+template <int NR>
+__device__ __forceinline__ void aes_keyed_chain(uint32_t* p, const AesKeyEntry* k, uint32_t j, uint64_t nblk,
+                                                const uint32_t* tab) {
+    uint32_t rk[NR + 1];
+#pragma unroll
+    for (int r = 0; r <= NR; r++) rk[r] = k->w[4 * r + j];
+    uint32_t c = k->iv[j];
+    const uint64_t total = nblk + 1;   // the padding block comes after the data
+    uint32_t pf[kAesDepth];
+#pragma unroll
+    for (int i = 0; i < kAesDepth; i++) pf[i] = (uint64_t)i < nblk ? p[4 * i] : kAesPadWord;
+    for (uint64_t b0 = 0; b0 < total; b0 += kAesDepth) {
+#pragma unroll
+        for (int i = 0; i < kAesDepth; i++) {
+            const uint64_t b = b0 + i;
+            if (b >= total) break;
+            const uint32_t x = pf[i] ^ c;
+            // block b + kAesDepth (still plaintext: the chain has written blocks < b only)
+            pf[i] = b + kAesDepth < nblk ? p[4 * (b + kAesDepth)] : kAesPadWord;
+            c = aes_encrypt_quad<NR>(x, rk, tab);
+            p[4 * b] = c;
+        }
+    }
+}
+
+// Grid: one workgroup of one wave per 16 slots.  Every chain has nblk blocks and every chain of a
+// wave the same round count (read once, uniform: a scalar branch into one of three unrolled loops),
+// so the loop bounds are uniform over the wave; a quad is wholly a chain or wholly an empty slot.
+__global__ __launch_bounds__(kAesEncThreads)
+void aes_cbc_encrypt_keyed_kernel(AesKeyedArgs a) {
+    __shared__ uint32_t tab[5 * 256];
+    aes_fill_lds<kAesEncThreads>(tab, kAesTables.te0, kAesTables.sbox);
+    const uint32_t j = threadIdx.x & 3u;
+    const uint32_t nr = a.wave_rounds[blockIdx.x];
+    const AesChainSlot sl = a.slot[(uint64_t)blockIdx.x * (kAesEncThreads / kAesLanesPerChain) + threadIdx.x / kAesLanesPerChain];
+    if (!sl.dev) return;
+    uint32_t* p = reinterpret_cast<uint32_t*>(sl.dev) + j;   // this lane's column of block 0
+    const AesKeyEntry* k = a.keys + sl.key;
+    if (nr == 10)
+        aes_keyed_chain<10>(p, k, j, a.nblk, tab);
+    else if (nr == 12)
+        aes_keyed_chain<12>(p, k, j, a.nblk, tab);
+    else
+        aes_keyed_chain<14>(p, k, j, a.nblk, tab);
 }
 
 }  // namespace dm

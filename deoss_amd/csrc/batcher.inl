@@ -26,6 +26,8 @@ struct BatchReq : dm_batch::Req {
     void* frags_out = nullptr;      // PROCESS (nullable)
     uint8_t* seg_hashes = nullptr;  // PROCESS (nullable)
     uint8_t* frag_hashes = nullptr; // PROCESS (nullable)
+    const void* cipher = nullptr;   // PROCESS: the request's cipher (dm_batcher_process_cipher), length checked at submit
+    uint64_t cipher_len = 0;        // 0 = a plain request
 };
 
 thread_local std::string t_batcher_err;
@@ -84,15 +86,33 @@ int batch_process_host(dm_rs* r, const std::vector<BatchReq*>& reqs, uint64_t se
     std::vector<void*> frags(n);
     std::vector<uint8_t*> segh(n), fragh(n);
     std::vector<uint8_t> fids(32 * n);
+    std::vector<const void*> ciphers(n);
+    std::vector<uint64_t> cipher_lens(n);
+    bool any_cipher = false;
     for (uint64_t o = 0; o < n; o++) {
         ptrs[o] = reqs[o]->host;
         lens[o] = reqs[o]->len;
         frags[o] = reqs[o]->frags_out;
         segh[o] = reqs[o]->seg_hashes;
         fragh[o] = reqs[o]->frag_hashes;
+        ciphers[o] = reqs[o]->cipher;
+        cipher_lens[o] = reqs[o]->cipher_len;
+        any_cipher = any_cipher || cipher_lens[o] != 0;
     }
-    RC_TRY(process_host(r, c->devs[0], ptrs.data(), lens.data(), n, segment, frags.data(), segh.data(), fragh.data(),
-                        fids.data()));
+    if (any_cipher) {   // plain and encrypted requests in one pass, as dm_process_cipher_batch runs them
+        BatchKeys bk;
+        RC_TRY(batch_keys(c, ciphers.data(), cipher_lens.data(), n, bk));
+        Dev& d = c->devs[0];
+        const int rc = process_cipher_batch_host(r, d, bk, ptrs.data(), lens.data(), n, segment, frags.data(), segh.data(),
+                                                 fragh.data(), fids.data());
+        if (rc != DM_OK) {
+            (void)hipStreamSynchronize(d.stream);   // no copy from a caller's memory stays queued
+            return rc;
+        }
+    } else {
+        RC_TRY(process_host(r, c->devs[0], ptrs.data(), lens.data(), n, segment, frags.data(), segh.data(), fragh.data(),
+                            fids.data()));
+    }
     for (uint64_t o = 0; o < n; o++) std::memcpy(reqs[o]->out32, fids.data() + 32 * o, 32);
     return DM_OK;
 }
@@ -238,6 +258,42 @@ int dm_batcher_process(dm_batcher* b, const void* host, uint64_t len, void* frag
     r.frags_out = frags_out;
     r.seg_hashes = seg_hashes;
     r.frag_hashes = frag_hashes;
+    return batcher_submit(b, r);
+}
+
+int dm_batcher_process_cipher(dm_batcher* b, const void* host, uint64_t len, const void* cipher, uint64_t cipher_len,
+                              void* frags_out, uint8_t* seg_hashes, uint8_t* frag_hashes, uint8_t fid[32]) {
+    if (!cipher || cipher_len == 0) return dm_batcher_process(b, host, len, frags_out, seg_hashes, frag_hashes, fid);
+    if (!b || !fid || (!host && len) || b->mode != DM_BATCH_PROCESS) {
+        t_batcher_err = "dm_batcher_process_cipher: bad argument or not a PROCESS batcher";
+        return DM_ERR_INVALID;
+    }
+    if (len == 0) {
+        t_batcher_err = "Empty data";
+        return DM_ERR_EMPTY;
+    }
+    // refused here, before the request is queued: one client's bad cipher never fails another's batch
+    if (!dm_cipher::key_len_ok(cipher_len)) {
+        t_batcher_err = dm_cipher::kKeyLenError;
+        return DM_ERR_INVALID;
+    }
+    if (!dm_cipher::segment_ok(b->unit)) {
+        t_batcher_err = "dm_batcher_process_cipher: segment size has no room for a block and its padding block";
+        return DM_ERR_INVALID;
+    }
+    const uint64_t nseg = dm_cipher::geometry(len, b->unit).nseg;
+    BatchReq r;
+    r.host = host;
+    r.len = len;
+    r.leaves = nseg * (1 + (uint64_t)(b->k + b->m));
+    r.bytes = nseg * b->unit * 3;   // segments + parity in device memory
+    r.chain_bytes = b->unit;        // every segment is one full SHA-256 chain (the linger's estimate; the AES chain before it is not modelled)
+    r.out32 = fid;
+    r.frags_out = frags_out;
+    r.seg_hashes = seg_hashes;
+    r.frag_hashes = frag_hashes;
+    r.cipher = cipher;
+    r.cipher_len = cipher_len;
     return batcher_submit(b, r);
 }
 

@@ -5,9 +5,12 @@
 //
 // The cipher branch of cess-go-sdk process.FullProcessing / Retrievefile (cipher != ""): the scheme
 // is recalled, not pinned (cipher_scheme.hpp); the AES-CBC core is FIPS-197 /
-// SP 800-38A.  The key schedule runs on the host per call; the round keys are kernel arguments and
-// never sit in a device buffer.
+// SP 800-38A.  The key schedule runs on the host per call.  With one key per launch the round keys
+// are kernel arguments and never sit in a device buffer; the keyed launch (a key per chain:
+// launch_aes_encrypt_keyed) is the one place they do, in the lane's d.aes_keys, which is zeroed in
+// stream order right after the kernel and on every error path after the upload.
 #include "aes_kernels.hpp"
+#include "aes_keyed_plan.hpp"
 #include "cipher_scheme.hpp"
 
 namespace {
@@ -122,9 +125,100 @@ int launch_aes_decrypt_windows(dm_ctx* c, Dev& d, hipStream_t s, const CipherKey
     return DM_OK;
 }
 
+// A chain of a keyed launch: `plain` bytes at dev, encrypted in place under keys[key].
+struct KeyedChain {
+    uint8_t* dev;
+    uint32_t key;
+};
+
+// Chains with a key each (aes_cbc_encrypt_keyed_kernel): every chain has `plain` bytes and becomes
+// plain + 16 of ciphertext in place; ONE launch whatever the mix of keys and key lengths.  The
+// plan orders the slots so that a wave holds one round count; slot table and wave round counts go
+// to d.aes_win, the key table to d.aes_keys, both through the lane's bounce buffer.  The key table
+// is zeroed in stream order after the kernel, and when the launch fails after the upload.
+int launch_aes_encrypt_keyed(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<CipherKey>& keys,
+                             const std::vector<KeyedChain>& chains, uint64_t plain) {
+    if (chains.empty()) return DM_OK;
+    std::vector<int> rounds(chains.size());
+    for (size_t i = 0; i < chains.size(); i++) rounds[i] = keys[chains[i].key].ks.rounds;
+    dm_aes_plan::KeyedPlan plan;
+    if (!dm_aes_plan::keyed_plan(rounds.data(), rounds.size(), plan))
+        return fail(c, DM_ERR_INVALID, "%s", dm_cipher::kKeyLenError);
+    const uint64_t nslot = plan.slot.size(), nwave = plan.wave_rounds.size();
+    // one upload: the slots, then the waves' round counts
+    const uint64_t slot_bytes = nslot * sizeof(dm::AesChainSlot), tab_bytes = slot_bytes + nwave * sizeof(uint32_t);
+    std::vector<uint8_t> tab(tab_bytes);
+    dm::AesChainSlot* sl = reinterpret_cast<dm::AesChainSlot*>(tab.data());
+    for (uint64_t i = 0; i < nslot; i++) {
+        const int64_t ch = plan.slot[i];
+        sl[i] = ch < 0 ? dm::AesChainSlot{nullptr, 0u, 0u} : dm::AesChainSlot{chains[ch].dev, chains[ch].key, 0u};
+    }
+    for (uint64_t w = 0; w < nwave; w++) {
+        const uint32_t nr = (uint32_t)plan.wave_rounds[w];
+        std::memcpy(tab.data() + slot_bytes + 4 * w, &nr, 4);
+    }
+    std::vector<dm::AesKeyEntry> kt(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) {
+        std::memcpy(kt[i].w, keys[i].ks.enc, sizeof kt[i].w);
+        std::memcpy(kt[i].iv, keys[i].iv, 16);
+    }
+    const uint64_t key_bytes = kt.size() * sizeof(dm::AesKeyEntry);
+    RC_TRY(tables_begin(c, d, tab_bytes + key_bytes + 1024));
+    RC_TRY(upload(c, d, s, d.aes_win, tab.data(), tab_bytes));
+    const int up = upload(c, d, s, d.aes_keys, kt.data(), key_bytes);
+    std::memset(static_cast<void*>(kt.data()), 0, key_bytes);
+    hipError_t e = hipSuccess;
+    if (up == DM_OK) {
+        dm::AesKeyedArgs a{};
+        a.slot = reinterpret_cast<const dm::AesChainSlot*>(d.aes_win.u8());
+        a.keys = static_cast<const dm::AesKeyEntry*>(d.aes_keys.p);
+        a.wave_rounds = reinterpret_cast<const uint32_t*>(d.aes_win.u8() + slot_bytes);
+        a.nblk = plain / 16;
+        hipLaunchKernelGGL(dm::aes_cbc_encrypt_keyed_kernel, dim3((uint32_t)nwave), dim3(dm::kAesEncThreads), 0, s, a);
+        e = hipGetLastError();
+    }
+    // round keys do not outlive the launch in device memory (a failed upload may have copied some)
+    hipError_t z = hipSuccess;
+    if (d.aes_keys.p) z = hipMemsetAsync(d.aes_keys.p, 0, key_bytes, s);
+    RC_TRY(up);
+    HIP_TRY(e);
+    HIP_TRY(z);
+    return DM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dm_aes_cbc_encrypt_keyed_device_async(dm_ctx* ctx, const dm_aes_key* keys, uint64_t nkeys, const dm_aes_chain* chains,
+                                          uint64_t nchain, uint64_t plain, void* stream) {
+    if (!ctx || (nkeys && !keys)) return bad_arg();
+    const int g = device_of(ctx, nchain && chains ? chains[0].dev : nullptr);
+    CallLock lk(ctx, g, kReserved);
+    dm_ctx* c = ctx;
+    std::vector<CipherKey> ks(nkeys);
+    for (uint64_t i = 0; i < nkeys; i++) {
+        if (!keys[i].key || !dm_aes::expand_key(static_cast<const uint8_t*>(keys[i].key), keys[i].key_len, ks[i].ks))
+            return fail(c, DM_ERR_INVALID, "key %llu: %s", (unsigned long long)i, dm_cipher::kKeyLenError);
+        cipher_set_iv(ks[i], keys[i].iv);
+    }
+    if (nchain == 0) return DM_OK;
+    if (!chains) return fail(c, DM_ERR_INVALID, "dm_aes_cbc_encrypt_keyed_device_async: null chains");
+    if (plain % 16)
+        return fail(c, DM_ERR_INVALID, "dm_aes_cbc_encrypt_keyed_device_async: need plain %% 16 == 0");
+    std::vector<KeyedChain> ch(nchain);
+    for (uint64_t i = 0; i < nchain; i++) {
+        if (!chains[i].dev || !is_aligned16(chains[i].dev) || chains[i].key_index >= nkeys)
+            return fail(c, DM_ERR_INVALID,
+                        "dm_aes_cbc_encrypt_keyed_device_async: chain %llu needs a 16-byte aligned buffer and a key "
+                        "index below %llu", (unsigned long long)i, (unsigned long long)nkeys);
+        ch[i] = KeyedChain{static_cast<uint8_t*>(chains[i].dev), chains[i].key_index};
+    }
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    return launch_aes_encrypt_keyed(c, d, s, ks, ch, plain);
+}
 
 int dm_aes_cbc_decrypt_windows_device_async(dm_ctx* ctx, const void* key, uint64_t key_len, const uint8_t iv[16],
                                             const dm_aes_window* windows, uint64_t nwin, void* dev_pad_ok, void* stream) {

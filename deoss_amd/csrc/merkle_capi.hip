@@ -329,7 +329,8 @@ struct Dev {
     hipStream_t copy = nullptr;         // H2D stream
     DevBuf data, nodes_a, nodes_b, leaves, tab_addr, tab_len, tab_first, tab_ids, root, gather;
     DevBuf proof_paths, proof_bits, proof_roots;   // host-API proof staging (tree_capi.inl)
-    DevBuf aes_win;                     // window descriptors of a ranged decryption (cipher_capi.inl)
+    DevBuf aes_win;                     // window descriptors of a ranged decryption / chain slots of a keyed encryption (cipher_capi.inl)
+    DevBuf aes_keys;                    // key table of a keyed encryption: zeroed after every launch (cipher_capi.inl)
     PinnedBuf stage[2];
     PinnedBuf htab;                     // pinned bounce buffer for per-call index tables
     uint64_t htab_used = 0;
@@ -1241,7 +1242,8 @@ int root_device_impl(dm_ctx* c, Dev& d, hipStream_t s, const void* dev, uint64_t
 int init_device(dm_ctx* c, Dev& d) {
     HIP_TRY(hipSetDevice(d.id));
     for (DevBuf* b : {&d.data, &d.nodes_a, &d.nodes_b, &d.leaves, &d.tab_addr, &d.tab_len, &d.tab_first, &d.tab_ids,
-                      &d.root, &d.gather, &d.proof_paths, &d.proof_bits, &d.proof_roots, &d.aes_win}) {
+                      &d.root, &d.gather, &d.proof_paths, &d.proof_bits, &d.proof_roots, &d.aes_win,
+                      &d.aes_keys}) {
         b->rp = &c->reaper;   // scratch growth never synchronises the device (Reaper)
         b->dev = d.id;
     }
@@ -1279,7 +1281,8 @@ void destroy_device(Dev& d) {
     if (hipSetDevice(d.id) != hipSuccess) return;
     (void)hipDeviceSynchronize();
     for (DevBuf* b : {&d.data, &d.nodes_a, &d.nodes_b, &d.leaves, &d.tab_addr, &d.tab_len, &d.tab_first, &d.tab_ids,
-                      &d.root, &d.gather, &d.proof_paths, &d.proof_bits, &d.proof_roots, &d.aes_win})
+                      &d.root, &d.gather, &d.proof_paths, &d.proof_bits, &d.proof_roots, &d.aes_win,
+                      &d.aes_keys})
         b->release();
     d.stage[0].release();
     d.stage[1].release();

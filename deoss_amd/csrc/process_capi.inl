@@ -156,6 +156,89 @@ int process_cipher_host(dm_rs* r, Dev& d, const CipherKey& key, const uint8_t* h
     return process_staged(r, d, {0, g.nseg}, segment, &frags_out, &seg_hashes, &frag_hashes, fid);
 }
 
+// The keys of a batch whose objects carry a cipher each: key_of[o] indexes keys, -1 = a plain
+// object.  Objects with identical cipher bytes share an entry.
+struct BatchKeys {
+    std::vector<CipherKey> keys;
+    std::vector<int32_t> key_of;
+    bool any() const { return !keys.empty(); }
+};
+
+// Fills bk for nobj objects (ciphers / cipher_lens nullable: all plain).  A bad length fails naming
+// the object; nothing else is checked here.
+int batch_keys(dm_ctx* c, const void* const* ciphers, const uint64_t* cipher_lens, uint64_t nobj, BatchKeys& bk) {
+    bk.keys.clear();
+    bk.key_of.assign(nobj, -1);
+    if (!ciphers || !cipher_lens) return DM_OK;
+    std::vector<uint64_t> owner;   // the first object of each key entry
+    for (uint64_t o = 0; o < nobj; o++) {
+        if (!ciphers[o] || cipher_lens[o] == 0) continue;
+        if (!dm_cipher::key_len_ok(cipher_lens[o]))
+            return fail(c, DM_ERR_INVALID, "object %llu: %s", (unsigned long long)o, dm_cipher::kKeyLenError);
+        size_t e = 0;
+        while (e < owner.size() && (cipher_lens[owner[e]] != cipher_lens[o] ||
+                                    std::memcmp(ciphers[owner[e]], ciphers[o], cipher_lens[o]) != 0))
+            e++;
+        if (e == owner.size()) {
+            CipherKey k;
+            RC_TRY(cipher_key(c, ciphers[o], cipher_lens[o], k));
+            bk.keys.push_back(k);
+            owner.push_back(o);
+        }
+        bk.key_of[o] = (int32_t)e;
+    }
+    return DM_OK;
+}
+
+// process_host for objects with a cipher each (bk.key_of[o] < 0: a plain object of the same batch).
+// One staging pass: plain objects as process_host puts them down, encrypted ones as
+// process_cipher_host does (P = segment - 16 byte pieces at stride `segment`, the last piece zeroed
+// up to P); ONE keyed launch encrypts every encrypted object's pieces in place, whatever the mix
+// of keys; from there process_staged runs once over all segments.
+int process_cipher_batch_host(dm_rs* r, Dev& d, const BatchKeys& bk, const void* const* objs, const uint64_t* lens,
+                              uint64_t nobj, uint64_t segment, void* const* frags_out, uint8_t* const* seg_hashes,
+                              uint8_t* const* frag_hashes, uint8_t* fids) {
+    dm_ctx* c = r->c;
+    hipStream_t s = d.stream;
+    RC_TRY(begin_call(c, d, s));
+    const uint64_t piece = segment - dm_cipher::kBlock;
+    std::vector<uint64_t> first(nobj + 1, 0);
+    for (uint64_t o = 0; o < nobj; o++)
+        first[o + 1] = first[o] + (bk.key_of[o] < 0 ? ceil_div(lens[o], segment) : dm_cipher::geometry(lens[o], segment).nseg);
+    const uint64_t S = first[nobj];
+    HIP_TRY(d.data.ensure(S * segment + kAlign));
+    std::vector<const void*> pptr;
+    std::vector<uint64_t> plen, poff;
+    for (uint64_t o = 0; o < nobj; o++)
+        if (bk.key_of[o] < 0) {
+            pptr.push_back(objs[o]);
+            plen.push_back(lens[o]);
+            poff.push_back(first[o] * segment);
+        }
+    if (!pptr.empty()) RC_TRY(h2d_at(c, d, pptr.data(), plen.data(), pptr.size(), poff));
+    std::vector<KeyedChain> chains;
+    for (uint64_t o = 0; o < nobj; o++) {
+        uint8_t* base = d.data.u8() + first[o] * segment;
+        const uint64_t ns = first[o + 1] - first[o];
+        if (bk.key_of[o] < 0) {
+            const uint64_t pad = ns * segment - lens[o];
+            if (pad) HIP_TRY(hipMemsetAsync(base + lens[o], 0, pad, s));
+            continue;
+        }
+        const uint8_t* host = static_cast<const uint8_t*>(objs[o]);
+        const uint64_t full = lens[o] / piece, rem = lens[o] - full * piece;
+        if (full) HIP_TRY(hipMemcpy2DAsync(base, segment, host, piece, piece, full, hipMemcpyHostToDevice, s));
+        if (rem) {
+            uint8_t* last = base + full * segment;
+            HIP_TRY(hipMemcpyAsync(last, host + full * piece, rem, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(last + rem, 0, piece - rem, s));
+        }
+        for (uint64_t t = 0; t < ns; t++) chains.push_back(KeyedChain{base + t * segment, (uint32_t)bk.key_of[o]});
+    }
+    RC_TRY(launch_aes_encrypt_keyed(c, d, s, bk.keys, chains, piece));
+    return process_staged(r, d, first, segment, frags_out, seg_hashes, frag_hashes, fids);
+}
+
 int process_check(dm_rs* r, uint64_t len, uint64_t segment) {
     dm_ctx* c = r->c;
     if (len == 0) return fail(c, DM_ERR_EMPTY, "Empty data");
@@ -234,6 +317,32 @@ int dm_process_batch(dm_rs* r, const void* const* objs, const uint64_t* lens, ui
     }
     RC_TRY(process_check(r, lens[0], segment));
     return process_host(r, c->devs[g], objs, lens, nobj, segment, frags_out, seg_hashes, frag_hashes, fids);
+}
+
+int dm_process_cipher_batch(dm_rs* r, const void* const* objs, const uint64_t* lens, const void* const* ciphers,
+                            const uint64_t* cipher_lens, uint64_t nobj, uint64_t segment, void* const* frags_out,
+                            uint8_t* const* seg_hashes, uint8_t* const* frag_hashes, uint8_t* fids) {
+    if (!r) return bad_arg();
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_process_cipher_batch"));
+    if (nobj == 0) return DM_OK;
+    if (!objs || !lens || !fids) return fail(c, DM_ERR_INVALID, "dm_process_cipher_batch: null argument");
+    for (uint64_t o = 0; o < nobj; o++) {
+        if (lens[o] == 0) return fail(c, DM_ERR_EMPTY, "Empty data (object %llu has no bytes)", (unsigned long long)o);
+        if (!objs[o]) return fail(c, DM_ERR_INVALID, "object %llu: NULL pointer", (unsigned long long)o);
+    }
+    BatchKeys bk;
+    RC_TRY(batch_keys(c, ciphers, cipher_lens, nobj, bk));
+    RC_TRY(process_check(r, lens[0], segment));
+    if (bk.any() && !dm_cipher::segment_ok(segment))
+        return fail(c, DM_ERR_INVALID, "segment size %llu has no room for a block and its padding block",
+                    (unsigned long long)segment);
+    Dev& d = c->devs[g];
+    const int rc = process_cipher_batch_host(r, d, bk, objs, lens, nobj, segment, frags_out, seg_hashes, frag_hashes, fids);
+    if (rc != DM_OK) (void)hipStreamSynchronize(d.stream);   // no copy from the caller's memory stays queued
+    return rc;
 }
 
 }  // extern "C"

@@ -13,7 +13,8 @@ import ctypes
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
-from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, AesWindow, DeossMerkleError, RangeWindow, load_library
+from ._lib import (DM_ERR_EMPTY, DM_ERR_INVALID, AesChain, AesKey, AesWindow, DeossMerkleError, RangeWindow,
+                   load_library)
 
 RANGE_NO_PADDING_CHECK = 8                                          # DM_RANGE_NO_PADDING_CHECK
 RANGE_WIN_PREV_IV, RANGE_WIN_CHECK_PAD, RANGE_WIN_PAD_ONLY = 1, 2, 4   # DM_RANGE_WIN_*
@@ -247,6 +248,25 @@ class MerkleContext:
                                                                   ctypes.c_void_p(dev_ptr), stride, plain, nseg,
                                                                   blk_lo, blk_hi, ctypes.c_void_p(stream or None)),
                     "dm_aes_cbc_encrypt_range_device_async")
+
+    def aes_cbc_encrypt_keyed_device_async(self, keys, chains, plain: int, stream: int = 0) -> None:
+        """``dm_aes_cbc_encrypt_keyed_device_async``: ONE launch over ``chains`` = [(dev_ptr,
+        key_index)], chain c's ``plain`` bytes encrypted in place (PKCS#7 block appended) under
+        ``keys[key_index]`` = (key bytes, iv); keys of different lengths may share the launch."""
+        keep = []
+        karr = (AesKey * max(len(keys), 1))()
+        for i, (key, iv) in enumerate(keys):
+            if len(iv) != 16:
+                raise DeossMerkleError(DM_ERR_INVALID, "iv must be 16 bytes")
+            kb = ctypes.create_string_buffer(bytes(key), max(len(key), 1))
+            keep.append(kb)
+            karr[i].key = ctypes.addressof(kb)
+            karr[i].key_len = len(key)
+            karr[i].iv[:] = bytes(iv)
+        carr = (AesChain * max(len(chains), 1))(*[AesChain(p or None, k, 0) for p, k in chains])
+        self._check(self._L.dm_aes_cbc_encrypt_keyed_device_async(self._h, karr, len(keys), carr, len(chains), plain,
+                                                                  ctypes.c_void_p(stream or None)),
+                    "dm_aes_cbc_encrypt_keyed_device_async")
 
     def aes_cbc_decrypt_device_async(self, key: bytes, iv: bytes, dev_in: int, in_stride: int, cipher_bytes: int,
                                      nseg: int, dev_out: int, out_stride: int, dev_pad_ok: int,

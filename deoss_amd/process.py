@@ -107,21 +107,28 @@ class Processor:
                         "dm_process_buffer")
         return seg.raw[:32 * nseg], frag.raw[:32 * nseg * total], fid.raw, (frags.raw if frags is not None else None)
 
-    def process_batch(self, bufs, want_frags: bool = False):
+    def process_batch(self, bufs, want_frags: bool = False, ciphers=None):
         """``dm_process_batch``: many objects in one pass; list of (seg digests, frag digests, fid,
-        fragments or None) per object."""
+        fragments or None) per object.  With ``ciphers`` (one per object; empty or None = a plain
+        object) ``dm_process_cipher_batch``: the encrypted objects' pieces are encrypted in one
+        keyed launch, whatever the mix of keys, and every object is coded and named in the same pass."""
         n = len(bufs)
         if n == 0:
             return []
+        if ciphers is not None and len(ciphers) != n:
+            raise DeossMerkleError(DM_ERR_INVALID, "process_batch: one cipher per object")
+        keys = [_cipher_bytes(c) for c in ciphers] if ciphers is not None else [b""] * n
         total = self.k + self.m
-        srcs, segs, frs, fragss = [], [], [], []
+        srcs, segs, frs, fragss, nsegs = [], [], [], [], []
         ptrs = (ctypes.c_void_p * n)()
         lens = (ctypes.c_uint64 * n)()
         sp = (ctypes.c_void_p * n)()
         fp = (ctypes.c_void_p * n)()
         gp = (ctypes.c_void_p * n)()
         for i, b in enumerate(bufs):
-            nseg = (len(b) + self.segment - 1) // self.segment
+            piece = self.segment - CIPHER_BLOCK if keys[i] else self.segment
+            nseg = (len(b) + piece - 1) // piece
+            nsegs.append(nseg)
             src = ctypes.create_string_buffer(bytes(b), max(len(b), 1))
             srcs.append(src)
             ptrs[i] = ctypes.addressof(src)
@@ -137,11 +144,18 @@ class Processor:
                 fragss.append(None)
                 gp[i] = None
         fids = ctypes.create_string_buffer(32 * n)
-        self._check(self.ctx._L.dm_process_batch(self.enc._h, ptrs, lens, n, self.segment, gp, sp, fp, fids),
-                    "dm_process_batch")
+        if ciphers is None:
+            self._check(self.ctx._L.dm_process_batch(self.enc._h, ptrs, lens, n, self.segment, gp, sp, fp, fids),
+                        "dm_process_batch")
+        else:
+            kbufs = [ctypes.create_string_buffer(k, max(len(k), 1)) for k in keys]
+            kp = (ctypes.c_void_p * n)(*[ctypes.addressof(k) for k in kbufs])
+            kl = (ctypes.c_uint64 * n)(*[len(k) for k in keys])
+            self._check(self.ctx._L.dm_process_cipher_batch(self.enc._h, ptrs, lens, kp, kl, n, self.segment, gp, sp,
+                                                            fp, fids), "dm_process_cipher_batch")
         out = []
-        for i, b in enumerate(bufs):
-            nseg = (len(b) + self.segment - 1) // self.segment
+        for i in range(n):
+            nseg = nsegs[i]
             out.append((segs[i].raw[:32 * nseg], frs[i].raw[:32 * nseg * total], fids.raw[32 * i:32 * i + 32],
                         fragss[i].raw if fragss[i] is not None else None))
         return out

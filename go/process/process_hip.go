@@ -168,8 +168,11 @@ type window struct {
 }
 
 // runWindow reads the file, codes + hashes it through the batcher and writes its fragments to
-// savedir; the caller holds one budget slot.
-func runWindow(f *os.File, w *window, savedir string) {
+// savedir; the caller holds one budget slot.  With a cipher (16, 24 or 32 bytes) the request is
+// dm_batcher_process_cipher: w.nseg counts pieces of chain.SegmentSize - 16 bytes, the library
+// encrypts each into one segment (one keyed AES-CBC launch per coalesced batch, whatever keys the
+// other goroutines' requests carry) and the fragments and names are of the ciphertext.
+func runWindow(f *os.File, w *window, savedir string, cipher string) {
 	seg := uint64(chain.SegmentSize)
 	total := uint64(chain.DataShards + chain.ParShards)
 	frag := seg / uint64(chain.DataShards)
@@ -186,10 +189,22 @@ func runWindow(f *os.File, w *window, savedir string) {
 		w.err = err
 		return
 	}
+	var ckey unsafe.Pointer
+	if cipher != "" {
+		ckey = unsafe.Pointer(C.CString(cipher))
+		defer C.free(ckey)
+	}
 	runtime.LockOSThread()
-	rc := C.dm_batcher_process(batcher, unsafe.Pointer(&data[0]), C.uint64_t(w.n), unsafe.Pointer(&b.frags[0]),
-		(*C.uint8_t)(unsafe.Pointer(&b.segd[0])), (*C.uint8_t)(unsafe.Pointer(&b.fragd[0])),
-		(*C.uint8_t)(unsafe.Pointer(&w.fid[0])))
+	var rc C.int
+	if cipher != "" {
+		rc = C.dm_batcher_process_cipher(batcher, unsafe.Pointer(&data[0]), C.uint64_t(w.n), ckey,
+			C.uint64_t(len(cipher)), unsafe.Pointer(&b.frags[0]), (*C.uint8_t)(unsafe.Pointer(&b.segd[0])),
+			(*C.uint8_t)(unsafe.Pointer(&b.fragd[0])), (*C.uint8_t)(unsafe.Pointer(&w.fid[0])))
+	} else {
+		rc = C.dm_batcher_process(batcher, unsafe.Pointer(&data[0]), C.uint64_t(w.n), unsafe.Pointer(&b.frags[0]),
+			(*C.uint8_t)(unsafe.Pointer(&b.segd[0])), (*C.uint8_t)(unsafe.Pointer(&b.fragd[0])),
+			(*C.uint8_t)(unsafe.Pointer(&w.fid[0])))
+	}
 	if rc != C.DM_OK {
 		w.err = batcherError(rc)
 	}
@@ -249,14 +264,20 @@ func FullProcessing(file string, cipher string, savedir string) ([]chain.Segment
 		return nil, "", err
 	}
 	seg := uint64(chain.SegmentSize)
-	total := uint64(chain.DataShards + chain.ParShards)
 	nseg := (size + seg - 1) / seg
 	if nseg > windowSegments {
 		return fullProcessingLarge(file, savedir, nseg)
 	}
+	return fullProcessingWindow(f, "", savedir, nseg, size)
+}
+
+// fullProcessingWindow: a file of nseg <= windowSegments segments (with a cipher: pieces of
+// chain.SegmentSize - 16 bytes) as one request of the process-wide batcher.
+func fullProcessingWindow(f *os.File, cipher, savedir string, nseg, size uint64) ([]chain.SegmentDataInfo, string, error) {
+	total := uint64(chain.DataShards + chain.ParShards)
 	w := &window{nseg: nseg, n: int(size)}
 	acquireBudget(int(nseg))
-	runWindow(f, w, savedir)
+	runWindow(f, w, savedir, cipher)
 	releaseBudget(int(nseg))
 	defer func() {
 		if w.buf != nil {
@@ -307,8 +328,12 @@ func FullProcessingFiles(files []string, cipher string, savedir string) ([][]cha
 	return infos, fids, errs
 }
 
-// FullProcessingCipher (additive): FullProcessing(file, cipher, savedir) with a cipher on the GPU,
-// one dm_full_processing_cipher call on a pipeline lane -- the library reads the file in pieces of
+// FullProcessingCipher (additive): FullProcessing(file, cipher, savedir) with a cipher on the GPU.
+// A file of at most windowSegments pieces of chain.SegmentSize - 16 bytes is one request of the
+// process-wide batcher (dm_batcher_process_cipher): concurrent encrypted uploads, whatever their
+// keys, and plain ones coalesce into one pass with ONE keyed AES-CBC launch, so they share the
+// ~1.7 s an AES chain costs instead of taking a pipeline lane each.  A larger file is one
+// dm_full_processing_cipher call on a pipeline lane -- the library reads the file in pieces of
 // chain.SegmentSize - 16 bytes, AES-CBC encrypts each into one segment as its stripes land, codes
 // and names the ciphertext and writes every file.  PARITY-UNPINNED: the scheme is recalled from the
 // SDK, not confirmed against it (INTEGRATION.md "Encrypted uploads"), so FullProcessing does not
@@ -323,8 +348,21 @@ func FullProcessingCipher(file string, cipher string, savedir string) ([]chain.S
 		piece -= 16
 	}
 	nseg := uint64(1) // a missing or empty file: the library reports it in Go's words
+	size := uint64(0)
 	if st, err := os.Stat(file); err == nil && st.Size() > 0 {
-		nseg = (uint64(st.Size()) + piece - 1) / piece
+		size = uint64(st.Size())
+		nseg = (size + piece - 1) / piece
+	}
+	if cipher != "" && size > 0 && nseg <= windowSegments {
+		f, err := os.Open(file)
+		if err != nil {
+			return nil, "", err
+		}
+		defer f.Close()
+		if err = os.MkdirAll(savedir, 0755); err != nil {
+			return nil, "", err
+		}
+		return fullProcessingWindow(f, cipher, savedir, nseg, size)
 	}
 	return fullProcessingOneCall(file, cipher, savedir, nseg)
 }

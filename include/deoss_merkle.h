@@ -420,6 +420,28 @@ int dm_aes_cbc_encrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_l
 int dm_aes_cbc_encrypt_range_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16],
                                           void *dev, uint64_t stride, uint64_t plain, uint64_t nseg, uint64_t blk_lo,
                                           uint64_t blk_hi, void *stream);
+/* A key per chain: nchain chains anywhere in device memory (no common stride), every one `plain`
+ * bytes that become plain + 16 bytes of ciphertext in place, chain c under keys[chains[c].key_index]
+ * -- ONE launch whatever the mix of keys and key lengths (a coalesced batch holds different
+ * clients' uploads), so the call costs its longest chain, not the sum over keys.  The result equals
+ * dm_aes_cbc_encrypt_device_async per key.  The round keys travel in a table in the call lane's
+ * scratch, zeroed in stream order right after the kernel; both arrays may be released on return.
+ * A key length other than 16, 24 or 32 is DM_ERR_INVALID "key <i>: cipher must be 16, 24 or 32
+ * bytes"; chains must be non-null and 16-byte aligned with key_index < nkeys, plain % 16 == 0 (else
+ * DM_ERR_INVALID, nothing runs); chains must not overlap (plain + 16 bytes each).  nchain == 0 is a
+ * no-op. */
+typedef struct dm_aes_key {
+    const void *key;
+    uint64_t key_len;
+    uint8_t iv[16];
+} dm_aes_key;
+typedef struct dm_aes_chain {
+    void *dev;
+    uint32_t key_index;
+    uint32_t reserved;
+} dm_aes_chain;
+int dm_aes_cbc_encrypt_keyed_device_async(dm_ctx *ctx, const dm_aes_key *keys, uint64_t nkeys,
+                                          const dm_aes_chain *chains, uint64_t nchain, uint64_t plain, void *stream);
 /* Decrypt works out of place (the two buffers must not overlap): segment s's cipher_bytes at
  * dev_in + s*in_stride become cipher_bytes - 16 plaintext bytes at dev_out + s*out_stride (with
  * out_stride = cipher_bytes - 16 the output is the joined object), and dev_pad_ok[s] (one byte per
@@ -433,6 +455,18 @@ int dm_aes_cbc_decrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_l
 int dm_process_cipher_buffer(dm_rs *rs, const void *host, uint64_t len, uint64_t segment, const void *cipher,
                              uint64_t cipher_len, void *frags_out, uint8_t *seg_hashes, uint8_t *frag_hashes,
                              uint8_t fid[32]);
+/* dm_process_batch with a cipher per object (synchronous): ciphers[o] / cipher_lens[o] as in
+ * dm_process_cipher_buffer; a NULL cipher or cipher_lens[o] == 0 is a plain object of the same batch
+ * (ciphers or cipher_lens NULL: every object is plain, the call is dm_process_batch).  Every
+ * encrypted object's pieces are encrypted in ONE keyed launch (dm_aes_cbc_encrypt_keyed_device_async),
+ * then every segment of every object is coded and named in one pass; per-object outputs are those
+ * of dm_process_cipher_buffer / dm_process_buffer of the object alone (an encrypted object has
+ * ceil(len / (segment - 16)) segments).  Everything is checked before anything runs: an empty
+ * object is DM_ERR_EMPTY and a bad cipher length DM_ERR_INVALID, both naming the object, and no
+ * output is written. */
+int dm_process_cipher_batch(dm_rs *rs, const void *const *objs, const uint64_t *lens, const void *const *ciphers,
+                            const uint64_t *cipher_lens, uint64_t nobj, uint64_t segment, void *const *frags_out,
+                            uint8_t *const *seg_hashes, uint8_t *const *frag_hashes, uint8_t *fids);
 /* dm_full_processing with a cipher: FullProcessing(file, cipher, savedir) from the file path in one
  * call.  cipher_len == 0 is dm_full_processing; any other length but 16, 24 or 32 is DM_ERR_INVALID
  * before savedir is touched.  The file's P-byte pieces are read at the segment pitch into a window
@@ -637,6 +671,12 @@ void dm_batcher_destroy(dm_batcher *b);
 int dm_batcher_root(dm_batcher *b, const void *host, uint64_t len, uint8_t *leaf_out, uint8_t root[32]);
 int dm_batcher_process(dm_batcher *b, const void *host, uint64_t len, void *frags_out, uint8_t *seg_hashes,
                        uint8_t *frag_hashes, uint8_t fid[32]);
+/* dm_batcher_process with a cipher (a DM_BATCH_PROCESS batcher; cipher_len == 0: dm_batcher_process):
+ * same outputs as dm_process_cipher_buffer.  Plain and encrypted requests coalesce into one pass
+ * (dm_process_cipher_batch).  The cipher's length and the segment size are checked before the
+ * request is queued, so a bad cipher fails its own call only. */
+int dm_batcher_process_cipher(dm_batcher *b, const void *host, uint64_t len, const void *cipher, uint64_t cipher_len,
+                              void *frags_out, uint8_t *seg_hashes, uint8_t *frag_hashes, uint8_t fid[32]);
 /* Requests served, batches launched, largest batch (requests). */
 int dm_batcher_stats(dm_batcher *b, uint64_t *requests, uint64_t *batches, uint64_t *max_batch);
 /* Message of the calling thread's last failing dm_batcher_* call. */

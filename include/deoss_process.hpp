@@ -191,6 +191,60 @@ inline Result FullProcessingCipher(const std::string& file, const std::string& c
     return {infos(savedir, segd_all, fragd_all, nseg_all), hex32(fid), std::nullopt};
 }
 
+// The batch form: objects in memory, a cipher each ("" = a plain object of the same batch), ONE
+// dm_process_cipher_batch call -- every encrypted object's pieces in one keyed AES-CBC launch
+// whatever the mix of keys, then every segment coded and named in one pass.  What a handler that
+// already holds several small encrypted uploads calls; concurrent handlers with one upload each
+// take dm_batcher_process_cipher.  Per object: the segment digests, the fragment digests, the hex
+// fid and (want_frags) the fragments, segment-major, data fragments first -- the outputs of
+// dm_process_cipher_buffer / dm_process_buffer of the object alone.  PARITY-UNPINNED as above.
+struct BatchObject {
+    const void* data = nullptr;
+    uint64_t len = 0;
+    std::string cipher;
+};
+
+struct BatchOutput {
+    std::vector<uint8_t> seg_hashes, frag_hashes, frags;
+    std::string fid;
+};
+
+using BatchResult = std::pair<std::vector<BatchOutput>, std::optional<Error>>;
+
+inline BatchResult FullProcessingCipherBatch(const std::vector<BatchObject>& objs, bool want_frags = true,
+                                             uint64_t segment = SegmentSize) {
+    auto& p = Pipelines::instance();
+    dm_rs* rs = p.pick();
+    if (!rs) return {{}, Error{p.status(), dm_strerror(p.status())}};
+    const uint64_t n = objs.size(), total = DataShards + ParShards;
+    if (segment <= 16) return {{}, Error{DM_ERR_INVALID, "process: segment too small for a cipher"}};
+    std::vector<BatchOutput> out(n);
+    std::vector<const void*> ptrs(n), keys(n);
+    std::vector<uint64_t> lens(n), key_lens(n);
+    std::vector<void*> fr(n);
+    std::vector<uint8_t*> sh(n), fh(n);
+    std::vector<uint8_t> fids(32 * n);
+    for (uint64_t o = 0; o < n; o++) {
+        const uint64_t piece = objs[o].cipher.empty() ? segment : segment - 16;
+        const uint64_t ns = (objs[o].len + piece - 1) / piece;
+        ptrs[o] = objs[o].data;
+        lens[o] = objs[o].len;
+        keys[o] = objs[o].cipher.empty() ? nullptr : objs[o].cipher.data();
+        key_lens[o] = objs[o].cipher.size();
+        out[o].seg_hashes.resize(32 * ns);
+        out[o].frag_hashes.resize(32 * ns * total);
+        if (want_frags) out[o].frags.resize(ns * total * (segment / DataShards));
+        sh[o] = out[o].seg_hashes.data();
+        fh[o] = out[o].frag_hashes.data();
+        fr[o] = want_frags ? out[o].frags.data() : nullptr;
+    }
+    const int rc = dm_process_cipher_batch(rs, ptrs.data(), lens.data(), keys.data(), key_lens.data(), n, segment, fr.data(),
+                                           sh.data(), fh.data(), fids.data());
+    if (rc != DM_OK) return {{}, last_error(rc)};
+    for (uint64_t o = 0; o < n; o++) out[o].fid = hex32(fids.data() + 32 * o);
+    return {std::move(out), std::nullopt};
+}
+
 // FullProcessing(file, cipher, savedir): one dm_full_processing call (the library reads the file
 // and writes every fragment and segment file to savedir/<hex SHA-256>); with a cipher,
 // dm_full_processing_cipher, the same call over segments of ciphertext.  `segment` is
