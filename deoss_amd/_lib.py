@@ -45,6 +45,7 @@ EXPORTS = (
     "dm_restore_cipher_buffer", "dm_aes_cbc_encrypt_range_device_async", "dm_full_processing_cipher",
     "dm_range_plan", "dm_aes_cbc_decrypt_windows_device_async", "dm_restore_range_buffer", "dm_retrieve_range",
     "dm_aes_cbc_encrypt_keyed_device_async", "dm_process_cipher_batch", "dm_batcher_process_cipher",
+    "dm_aes_cbc_decrypt_keyed_device_async", "dm_restore_batch", "dm_batcher_restore",
     "dm_pstream_open", "dm_pstream_write", "dm_pstream_close", "dm_pstream_abort",
     "dm_tree_node_count", "dm_tree_depth", "dm_tree_levels_device_async", "dm_tree_levels",
     "dm_merkle_paths_device_async", "dm_merkle_paths", "dm_verify_paths_device_async", "dm_verify_paths",
@@ -77,10 +78,47 @@ class AesChain(ctypes.Structure):
     _fields_ = [("dev", ctypes.c_void_p), ("key_index", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class AesDChain(ctypes.Structure):
+    """dm_aes_dchain: one chain of a keyed decryption on the device (in, out) and the index of its key."""
+    _fields_ = [("dev_in", ctypes.c_void_p), ("dev_out", ctypes.c_void_p), ("key_index", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class RestoreObj(ctypes.Structure):
+    """dm_restore_obj: one object of dm_restore_batch."""
+    _fields_ = [("frags", ctypes.POINTER(ctypes.c_void_p)), ("frag_names", ctypes.c_void_p),
+                ("seg_names", ctypes.c_void_p), ("fid", ctypes.c_void_p), ("nseg", ctypes.c_uint64),
+                ("size", ctypes.c_uint64), ("flags", ctypes.c_int), ("cipher", ctypes.c_void_p),
+                ("cipher_len", ctypes.c_uint64), ("out", ctypes.c_void_p), ("frag_status", ctypes.c_void_p),
+                ("seg_status", ctypes.c_void_p)]
+
+
 class DeossMerkleError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(message)
         self.code = code
+
+
+def restore_obj_fields(frags, size, frag_names, seg_names, fid, flags, key, total, frag_len):
+    """(RestoreObj, nseg, out, fst, sst, keep-alive list) of one object in ctypes."""
+    flat = [f for seg in frags for f in seg] if frags and isinstance(frags[0], (list, tuple)) else list(frags)
+    if len(flat) % total:
+        raise DeossMerkleError(DM_ERR_INVALID, "need data + parity entries per segment")
+    nseg = len(flat) // total
+    keep = [ctypes.create_string_buffer(bytes(f), len(f)) if f is not None else None for f in flat]
+    for b in keep:
+        if b is not None and len(b) != frag_len:
+            raise DeossMerkleError(DM_ERR_INVALID, "fragment sizes do not match")
+    ptrs = (ctypes.c_void_p * max(len(flat), 1))(*[ctypes.addressof(b) if b is not None else None for b in keep])
+    names = [ctypes.create_string_buffer(bytes(x), len(x)) if x else None for x in (frag_names, seg_names, fid)]
+    kbuf = ctypes.create_string_buffer(key, len(key)) if key else None
+    out = ctypes.create_string_buffer(max(size, 1))
+    fst = ctypes.create_string_buffer(max(nseg * total, 1))
+    sst = ctypes.create_string_buffer(max(nseg, 1))
+    adr = lambda b: ctypes.addressof(b) if b is not None else None  # noqa: E731
+    o = RestoreObj(ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p)), adr(names[0]), adr(names[1]), adr(names[2]),
+                   nseg, size, flags, adr(kbuf), len(key), adr(out), adr(fst), adr(sst))
+    return o, nseg, out, fst, sst, (keep, ptrs, names, kbuf)
 
 
 _lock = threading.Lock()
@@ -163,6 +201,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "dm_range_plan": ([u64, u64, u64, i32, i32, u64, u64, i32, pu64, pu64, vp, u64, vp, u64, pu64], i32),
         "dm_aes_cbc_decrypt_windows_device_async": ([vp, vp, u64, vp, vp, u64, vp, vp], i32),
         "dm_aes_cbc_encrypt_keyed_device_async": ([vp, vp, u64, vp, u64, u64, vp], i32),
+        "dm_aes_cbc_decrypt_keyed_device_async": ([vp, vp, u64, vp, u64, u64, vp, vp], i32),
+        "dm_restore_batch": ([vp, vp, u64, u64, ctypes.POINTER(i32)], i32),
+        "dm_batcher_restore": ([vp, pvp, vp, vp, vp, u64, u64, i32, vp, u64, vp, vp, vp, ctypes.POINTER(i32)], i32),
         "dm_process_cipher_batch": ([vp, pvp, pu64, pvp, pu64, u64, u64, pvp, pvp, pvp, vp], i32),
         "dm_batcher_process_cipher": ([vp, vp, u64, vp, u64, vp, vp, vp, vp], i32),
         "dm_restore_range_buffer": ([vp, pvp, vp, u64, u64, u64, u64, u64, i32, vp, u64, vp, vp, vp,

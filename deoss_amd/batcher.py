@@ -12,10 +12,11 @@ from __future__ import annotations
 import ctypes
 from typing import Optional, Tuple
 
-from ._lib import DM_ERR_EMPTY, DeossMerkleError, load_library
+from ._lib import DM_ERR_EMPTY, DeossMerkleError, load_library, restore_obj_fields
 
 ROOT = 0
 PROCESS = 1
+RESTORE = 2
 
 
 class Batcher:
@@ -98,6 +99,21 @@ class Batcher:
         else:
             self._check(self._L.dm_batcher_process(self._h, src, n, frags, seg, frag, fid), "dm_batcher_process")
         return seg.raw[:32 * nseg], frag.raw[:32 * nseg * total], fid.raw, (frags.raw if frags is not None else None)
+
+    def restore(self, frags, size: int, frag_names: Optional[bytes] = None, seg_names: Optional[bytes] = None,
+                fid: Optional[bytes] = None, flags: int = 7, cipher=b"") -> Tuple[bool, Optional[bytes], bytes, bytes]:
+        """A verified restore of one object through a RESTORE batcher (``dm_batcher_restore``):
+        arguments and result as :meth:`Processor.restore_buffer` -- (ok, the object's bytes or None,
+        fragment statuses, segment statuses).  Whatever is queued runs as one ``dm_restore_batch``."""
+        total = self.k + self.m
+        key = cipher.encode() if isinstance(cipher, str) else bytes(cipher or b"")
+        o, nseg, dst, fst, sst, _keep = restore_obj_fields(frags, size, frag_names, seg_names, fid, flags, key, total,
+                                                          self.unit // self.k)
+        ok = ctypes.c_int(0)
+        self._check(self._L.dm_batcher_restore(self._h, o.frags, o.frag_names, o.seg_names, o.fid, nseg, size, flags,
+                                               o.cipher, len(key), dst, fst, sst, ctypes.byref(ok)),
+                    "dm_batcher_restore")
+        return bool(ok.value), (dst.raw[:size] if ok.value else None), fst.raw[:nseg * total], sst.raw[:nseg]
 
     def stats(self) -> Tuple[int, int, int]:
         """(requests served, batches launched, largest batch in requests)."""

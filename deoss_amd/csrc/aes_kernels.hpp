@@ -28,6 +28,10 @@
 //       tables in device memory, a wave holds chains of one round count (aes_keyed_plan.hpp) and
 //       branches once into the loop unrolled for it, so ONE launch encrypts a batch of different
 //       clients' uploads (dm_process_cipher_batch, the batcher) in the time of its longest chain.
+//   aes_cbc_decrypt_keyed_kernel  aes_cbc_decrypt_kernel's block work with a key per chain: chain
+//       descriptors (in, out, key index, round count) and keys come from tables in device memory
+//       by scalar loads, once per chain, the key again only when its index changes, so ONE launch
+//       decrypts a batch of different clients' downloads (dm_restore_batch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -400,6 +404,114 @@ void aes_cbc_encrypt_keyed_kernel(AesKeyedArgs a) {
         aes_keyed_chain<12>(p, k, j, a.nblk, tab);
     else
         aes_keyed_chain<14>(p, k, j, a.nblk, tab);
+}
+
+// ---- a key per chain, decrypt: different clients' downloads in ONE launch (dm_restore_batch) ----
+
+// One chain of a keyed decrypt: nblk ciphertext blocks at `in`, nblk - 1 plaintext blocks to `out`
+// (anywhere: no common stride, so one object's pieces join back to back while another's lie
+// elsewhere) under key table entry `key`, whose round count the host repeats here.
+struct AesDChain {
+    const uint8_t* in;
+    uint8_t* out;
+    uint32_t key;
+    uint32_t rounds;   // 10, 12 or 14
+    uint64_t pad_;
+};
+static_assert(sizeof(AesDChain) == 32, "one 32-byte descriptor per chain");
+
+// Addresses read out of a table have no address space the compiler can see; without these casts
+// they become flat accesses (seen in the disassembly), which by the ISA's rules count against the
+// LDS lookups' wait counter as well -- reasoned from the ISA, the cost was not measured.
+typedef uint32_t aes_u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) aes_u32x4 aes_gu32x4;
+
+__device__ __forceinline__ uint4 aes_gload16(const uint8_t* p) {
+    const aes_u32x4 v = *(const aes_gu32x4*)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ void aes_gstore16(uint8_t* p, uint4 v) {   // non-temporal, as rs_store
+    const aes_u32x4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, (aes_gu32x4*)p);
+}
+
+// The block loop of aes_cbc_decrypt_kernel for one chain: one lane per block, the next stride's
+// loads in flight, the padding block checked by the lane that owns it and not stored.  Only the lane
+// of block 0 needs the IV: it loads it from the key entry, the others their predecessor block.
+template <int NR>
+__device__ __forceinline__ void aes_dkeyed_blocks(const uint8_t* in, uint8_t* out, uint32_t nblk, uint32_t ustride,
+                                                  const AesKey& dk, const uint32_t* iv, const uint32_t* tab,
+                                                  uint8_t* pad_ok) {
+    uint32_t u = blockIdx.x * kAesDecThreads + threadIdx.x;
+    if (u >= nblk) return;
+    // per-lane cursors: the chain's base addresses need not outlive this line in scalar registers
+    const uint8_t* pi = in + (uint64_t)u * 16;
+    uint8_t* po = out + (uint64_t)u * 16;
+    const uint32_t step = ustride * 16;   // rs_grid keeps a row of workgroups far below 4 GiB of blocks
+    uint4 nc = aes_gload16(pi), np = aes_gload16(u ? pi - 16 : reinterpret_cast<const uint8_t*>(iv));
+    for (;;) {
+        const uint4 cblk = nc, prev = np;
+        const bool more = nblk - u > ustride;   // no u + ustride: it may wrap
+        if (more) {
+            nc = aes_gload16(pi + step);
+            np = aes_gload16(pi + step - 16);
+        }
+        uint4 x = aes_decrypt_block<NR>(cblk, dk, tab);
+        x.x ^= prev.x;
+        x.y ^= prev.y;
+        x.z ^= prev.z;
+        x.w ^= prev.w;
+        if (u + 1 < nblk)
+            aes_gstore16(po, x);
+        else
+            *pad_ok = (x.x == kAesPadWord && x.y == kAesPadWord && x.z == kAesPadWord && x.w == kAesPadWord) ? 1 : 0;
+        if (!more) break;
+        u += ustride;
+        pi += step;
+        po += step;
+    }
+}
+
+constexpr int kAesDKeyedVWords = 12;
+
+// Grid: x strides over a chain's blocks, y over chains (rs_grid), as aes_cbc_decrypt_kernel; every
+// chain has nblk blocks (>= 2: the last one is the padding block; the host keeps nblk and nchain
+// within 32 bits).  Descriptor and key entry depend on the chain alone: both tables are read-only
+// for the launch and their addresses uniform over the workgroup, so they arrive by scalar loads,
+// once per chain -- the key only when the chain's key index is not the previous chain's
+// (rs_restore_kernel reloads its table on the same rule).  The round count is uniform too: one
+// scalar branch per chain into the loop unrolled for it, so the round keys are indexed at compile
+// time and stay in scalar registers.
+__global__ __launch_bounds__(kAesDecThreads)
+void aes_cbc_decrypt_keyed_kernel(const AesDChain* __restrict__ chains, const AesKeyEntry* __restrict__ keys,
+                                  uint32_t nchain, uint32_t nblk, uint8_t* __restrict__ pad_ok) {
+    __shared__ uint32_t tab[5 * 256];
+    aes_fill_lds<kAesDecThreads>(tab, kAesTables.td0, kAesTables.inv);
+    const uint32_t ustride = gridDim.x * kAesDecThreads;
+    AesKey dk;
+    uint32_t loaded = 0xffffffffu;   // no key's index
+    for (uint32_t ch = blockIdx.y; ch < nchain; ch += gridDim.y) {
+        const AesDChain d = chains[ch];
+        const AesKeyEntry* k = keys + d.key;
+        if (d.key != loaded) {
+#pragma unroll
+            for (int i = 0; i < dm_aes::kMaxKeyWords; i++) dk.w[i] = k->w[i];
+            // 60 key words, three chain-invariant pointers and the loop's masks do not all fit the
+            // scalar file: the first kAesDKeyedVWords words live in vector registers instead.  The
+            // count is what this compiler needs to reach 0 spills (102 SGPRs); the guard is
+            // tests/test_aes_dkeyed_codeobj.py, which fails on any spill or private segment.
+#pragma unroll
+            for (int i = 0; i < kAesDKeyedVWords; i++) asm("" : "+v"(dk.w[i]));
+            loaded = d.key;
+        }
+        if (d.rounds == 10)
+            aes_dkeyed_blocks<10>(d.in, d.out, nblk, ustride, dk, k->iv, tab, pad_ok + ch);
+        else if (d.rounds == 12)
+            aes_dkeyed_blocks<12>(d.in, d.out, nblk, ustride, dk, k->iv, tab, pad_ok + ch);
+        else
+            aes_dkeyed_blocks<14>(d.in, d.out, nblk, ustride, dk, k->iv, tab, pad_ok + ch);
+    }
 }
 
 }  // namespace dm

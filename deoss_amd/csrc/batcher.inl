@@ -28,6 +28,8 @@ struct BatchReq : dm_batch::Req {
     uint8_t* frag_hashes = nullptr; // PROCESS (nullable)
     const void* cipher = nullptr;   // PROCESS: the request's cipher (dm_batcher_process_cipher), length checked at submit
     uint64_t cipher_len = 0;        // 0 = a plain request
+    dm_restore_obj rst{};           // RESTORE: the request as dm_restore_batch takes it (checked at submit)
+    int* rst_ok = nullptr;          // RESTORE
 };
 
 thread_local std::string t_batcher_err;
@@ -117,6 +119,20 @@ int batch_process_host(dm_rs* r, const std::vector<BatchReq*>& reqs, uint64_t se
     return DM_OK;
 }
 
+// RESTORE batch on one slot: the pass dm_restore_batch runs.  Every request was checked at submit,
+// so nothing here fails for one request's arguments; a failed verification is that request's ok = 0.
+int batch_restore_host(dm_rs* r, const std::vector<BatchReq*>& reqs, uint64_t segment) {
+    dm_ctx* c = r->c;
+    CallLock lk(c, 0);
+    const uint64_t n = reqs.size();
+    std::vector<dm_restore_obj> objs(n);
+    std::vector<int> ok(n, 0);
+    for (uint64_t o = 0; o < n; o++) objs[o] = reqs[o]->rst;
+    const int rc = restore_batch_run(r, c->devs[0], objs.data(), n, segment, ok.data());
+    for (uint64_t o = 0; o < n; o++) *reqs[o]->rst_ok = rc == DM_OK ? ok[o] : 0;
+    return rc;
+}
+
 void batcher_worker(dm_batcher* b, size_t slot) {
     dm_ctx* c = b->ctxs[slot];
     std::vector<dm_batch::Req*> taken;
@@ -124,8 +140,9 @@ void batcher_worker(dm_batcher* b, size_t slot) {
     while (b->q->take(taken)) {
         batch.clear();
         for (dm_batch::Req* r : taken) batch.push_back(static_cast<BatchReq*>(r));
-        const int rc = b->mode == DM_BATCH_PROCESS ? batch_process_host(b->coders[slot], batch, b->unit)
-                                                   : batch_roots_host(c, batch, b->unit);
+        const int rc = b->mode == DM_BATCH_PROCESS   ? batch_process_host(b->coders[slot], batch, b->unit)
+                       : b->mode == DM_BATCH_RESTORE ? batch_restore_host(b->coders[slot], batch, b->unit)
+                                                     : batch_roots_host(c, batch, b->unit);
         b->q->finish(taken, rc, rc == DM_OK ? std::string() : c->err);
     }
 }
@@ -169,11 +186,12 @@ int dm_batcher_create(const int* devs, int ndev, int mode, uint64_t unit, int da
         }
         for (int i = 0; i < n; i++) dl.push_back(i);
     }
-    if (dl.empty() || (mode != DM_BATCH_ROOT && mode != DM_BATCH_PROCESS) || unit == 0 || slots < 0 || slots > 8) {
+    if (dl.empty() || (mode != DM_BATCH_ROOT && mode != DM_BATCH_PROCESS && mode != DM_BATCH_RESTORE) || unit == 0 || slots < 0 || slots > 8) {
         t_batcher_err = "dm_batcher_create: bad mode, unit or slot count";
         return DM_ERR_INVALID;
     }
-    if (mode == DM_BATCH_PROCESS && (data_shards < 1 || unit % (16ull * (uint64_t)data_shards))) {
+    const bool coded = mode == DM_BATCH_PROCESS || mode == DM_BATCH_RESTORE;   // unit = segment size, one dm_rs per slot
+    if (coded && (data_shards < 1 || unit % (16ull * (uint64_t)data_shards))) {
         t_batcher_err = "dm_batcher_create: segment must be a non-zero multiple of 16 x data shards";
         return DM_ERR_INVALID;
     }
@@ -198,7 +216,7 @@ int dm_batcher_create(const int* devs, int ndev, int mode, uint64_t unit, int da
             return rc;
         }
         b->ctxs.push_back(c);
-        if (mode == DM_BATCH_PROCESS) {
+        if (coded) {
             dm_rs* r = nullptr;
             rc = dm_rs_create(c, data_shards, parity_shards, &r);
             if (rc != DM_OK) {
@@ -294,6 +312,60 @@ int dm_batcher_process_cipher(dm_batcher* b, const void* host, uint64_t len, con
     r.frag_hashes = frag_hashes;
     r.cipher = cipher;
     r.cipher_len = cipher_len;
+    return batcher_submit(b, r);
+}
+
+int dm_batcher_restore(dm_batcher* b, const void* const* frags, const uint8_t* frag_names, const uint8_t* seg_names,
+                       const uint8_t* fid, uint64_t nseg, uint64_t size, int flags, const void* cipher,
+                       uint64_t cipher_len, void* out, uint8_t* frag_status, uint8_t* seg_status, int* ok) {
+    if (ok) *ok = 0;
+    if (!b || !ok || !frags || !out || b->mode != DM_BATCH_RESTORE) {
+        t_batcher_err = "dm_batcher_restore: bad argument or not a RESTORE batcher";
+        return DM_ERR_INVALID;
+    }
+    BatchReq r;
+    r.rst.frags = frags;
+    r.rst.frag_names = frag_names;
+    r.rst.seg_names = seg_names;
+    r.rst.fid = fid;
+    r.rst.nseg = nseg;
+    r.rst.size = size;
+    r.rst.flags = flags;
+    r.rst.cipher = cipher;
+    r.rst.cipher_len = cipher_len;
+    r.rst.out = out;
+    r.rst.frag_status = frag_status;
+    r.rst.seg_status = seg_status;
+    r.rst_ok = ok;
+    // refused here, before the request is queued: one client's bad request never fails another's batch
+    dm_restore_plan::Obj po;
+    po.frags = frags;
+    po.nseg = nseg;
+    po.size = size;
+    po.cipher = cipher;
+    po.cipher_len = cipher_len;
+    po.out = out;
+    if (po.encrypted() && !dm_cipher::key_len_ok(cipher_len)) {   // the keyed encrypt's text, as dm_batcher_process_cipher
+        t_batcher_err = dm_cipher::kKeyLenError;
+        return DM_ERR_INVALID;
+    }
+    if (nseg == 0) {
+        t_batcher_err = "Empty data";
+        return DM_ERR_EMPTY;
+    }
+    if (const dm_restore_plan::Error e = dm_restore_plan::check(&po, 1, b->unit, b->k)) {
+        const std::string who = "object 0: ";   // the request is its batch's only object: not named
+        t_batcher_err = "dm_batcher_restore: " + (e.msg.compare(0, who.size(), who) == 0 ? e.msg.substr(who.size()) : e.msg);
+        return e.code == dm_restore_plan::kEmpty ? DM_ERR_EMPTY : DM_ERR_INVALID;
+    }
+    const dm_restore_plan::Plan p = dm_restore_plan::plan(&po, 1, b->unit, b->k, b->m);
+    const uint64_t total = (uint64_t)(b->k + b->m);
+    for (uint64_t i = 0; i < nseg * total; i++) r.leaves += frags[i] != nullptr;   // phase 1 is the larger launch
+    r.leaves = std::max<uint64_t>(r.leaves, 1);
+    r.bytes = p.device_bytes();
+    const bool vfrag = (flags & DM_RESTORE_VERIFY_FRAGMENTS) && frag_names;
+    const bool vseg = ((flags & DM_RESTORE_VERIFY_SEGMENTS) && seg_names) || ((flags & DM_RESTORE_VERIFY_FID) && fid);
+    r.chain_bytes = vseg ? b->unit : vfrag ? p.frag : 64;   // the longest SHA-256 chain the request adds (none: one block)
     return batcher_submit(b, r);
 }
 

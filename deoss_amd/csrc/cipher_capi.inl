@@ -186,9 +186,93 @@ int launch_aes_encrypt_keyed(dm_ctx* c, Dev& d, hipStream_t s, const std::vector
     return DM_OK;
 }
 
+// A chain of a keyed decrypt: cipher_bytes at in -> cipher_bytes - 16 of plaintext at out, under keys[key].
+struct KeyedDChain {
+    const uint8_t* in;
+    uint8_t* out;
+    uint32_t key;
+};
+
+// Chains with a key each (aes_cbc_decrypt_keyed_kernel): every chain has cipher_bytes of ciphertext;
+// ONE launch whatever the mix of keys and key lengths, pad_ok[chain] on the device.  The chain table
+// goes to d.aes_win, the key table (the equivalent-inverse-cipher round keys) to d.aes_keys, both
+// through the lane's bounce buffer; the key table is zeroed in stream order after the kernel, and
+// when the launch fails after the upload, as launch_aes_encrypt_keyed does.
+int launch_aes_decrypt_keyed(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<CipherKey>& keys,
+                             const std::vector<KeyedDChain>& chains, uint64_t cipher_bytes, uint8_t* pad_ok) {
+    if (chains.empty()) return DM_OK;
+    if (chains.size() > 0xffffffffull || cipher_bytes / 16 > 0xffffffffull)   // the kernel counts both in 32 bits
+        return fail(c, DM_ERR_INVALID, "keyed decrypt: at most 2^32 - 1 chains of at most 2^32 - 1 blocks");
+    std::vector<dm::AesDChain> tab(chains.size());
+    for (size_t i = 0; i < chains.size(); i++)
+        tab[i] = dm::AesDChain{chains[i].in, chains[i].out, chains[i].key, (uint32_t)keys[chains[i].key].ks.rounds, 0};
+    std::vector<dm::AesKeyEntry> kt(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) {
+        std::memcpy(kt[i].w, keys[i].ks.dec, sizeof kt[i].w);
+        std::memcpy(kt[i].iv, keys[i].iv, 16);
+    }
+    const uint64_t tab_bytes = tab.size() * sizeof(dm::AesDChain), key_bytes = kt.size() * sizeof(dm::AesKeyEntry);
+    const int tb = tables_begin(c, d, tab_bytes + key_bytes + 1024);
+    if (tb != DM_OK) std::memset(static_cast<void*>(kt.data()), 0, key_bytes);
+    RC_TRY(tb);
+    int up = upload(c, d, s, d.aes_win, tab.data(), tab_bytes);
+    const bool keys_sent = up == DM_OK;
+    if (up == DM_OK) up = upload(c, d, s, d.aes_keys, kt.data(), key_bytes);
+    std::memset(static_cast<void*>(kt.data()), 0, key_bytes);
+    hipError_t e = hipSuccess;
+    if (up == DM_OK) {
+        const uint64_t nblk = cipher_bytes / 16;
+        const dim3 grid = rs_grid(d, nblk, chains.size()), block(dm::kAesDecThreads);
+        hipLaunchKernelGGL(dm::aes_cbc_decrypt_keyed_kernel, grid, block, 0, s,
+                           static_cast<const dm::AesDChain*>(d.aes_win.p), static_cast<const dm::AesKeyEntry*>(d.aes_keys.p),
+                           (uint32_t)chains.size(), (uint32_t)nblk, pad_ok);
+        e = hipGetLastError();
+    }
+    // round keys do not outlive the launch in device memory (a failed upload may have copied some)
+    hipError_t z = hipSuccess;
+    if (keys_sent && d.aes_keys.p) z = hipMemsetAsync(d.aes_keys.p, 0, key_bytes, s);
+    RC_TRY(up);
+    HIP_TRY(e);
+    HIP_TRY(z);
+    return DM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dm_aes_cbc_decrypt_keyed_device_async(dm_ctx* ctx, const dm_aes_key* keys, uint64_t nkeys, const dm_aes_dchain* chains,
+                                          uint64_t nchain, uint64_t cipher_bytes, void* dev_pad_ok, void* stream) {
+    if (!ctx || (nkeys && !keys)) return bad_arg();
+    const int g = device_of(ctx, nchain && chains ? chains[0].dev_in : nullptr);
+    CallLock lk(ctx, g, kReserved);
+    dm_ctx* c = ctx;
+    std::vector<CipherKey> ks(nkeys);
+    for (uint64_t i = 0; i < nkeys; i++) {
+        if (!keys[i].key || !dm_aes::expand_key(static_cast<const uint8_t*>(keys[i].key), keys[i].key_len, ks[i].ks))
+            return fail(c, DM_ERR_INVALID, "key %llu: %s", (unsigned long long)i, dm_cipher::kKeyLenError);
+        cipher_set_iv(ks[i], keys[i].iv);
+    }
+    if (nchain == 0) return DM_OK;
+    if (!chains || !dev_pad_ok)
+        return fail(c, DM_ERR_INVALID, "dm_aes_cbc_decrypt_keyed_device_async: null chains or verdict buffer");
+    if (cipher_bytes % 16 || cipher_bytes < 32)
+        return fail(c, DM_ERR_INVALID,
+                    "dm_aes_cbc_decrypt_keyed_device_async: need cipher_bytes %% 16 == 0 and cipher_bytes >= 32");
+    std::vector<KeyedDChain> ch(nchain);
+    for (uint64_t i = 0; i < nchain; i++) {
+        const dm_aes_dchain& x = chains[i];
+        if (!x.dev_in || !x.dev_out || !is_aligned16(x.dev_in) || !is_aligned16(x.dev_out) || x.key_index >= nkeys)
+            return fail(c, DM_ERR_INVALID,
+                        "dm_aes_cbc_decrypt_keyed_device_async: chain %llu needs 16-byte aligned in and out and a key "
+                        "index below %llu", (unsigned long long)i, (unsigned long long)nkeys);
+        ch[i] = KeyedDChain{static_cast<const uint8_t*>(x.dev_in), static_cast<uint8_t*>(x.dev_out), x.key_index};
+    }
+    Dev& d = c->devs[g];
+    hipStream_t s = pick_stream(d, stream);
+    RC_TRY(begin_call(c, d, s));
+    return launch_aes_decrypt_keyed(c, d, s, ks, ch, cipher_bytes, static_cast<uint8_t*>(dev_pad_ok));
+}
 
 int dm_aes_cbc_encrypt_keyed_device_async(dm_ctx* ctx, const dm_aes_key* keys, uint64_t nkeys, const dm_aes_chain* chains,
                                           uint64_t nchain, uint64_t plain, void* stream) {

@@ -19,6 +19,8 @@
 // Steps 2 - 4 are rt_check_frags and rt_rebuild for both paths; they take addresses, and each path
 // keeps its own layout of the parity fragments and its own policy after a failed check.
 
+#include "restore_batch_plan.hpp"
+
 namespace {
 
 constexpr uint64_t kRtWindowBytes = 1ull << 30;   // dm_retrieve_file: segment bytes per GPU pass (+ 2x parity scratch)
@@ -68,6 +70,28 @@ struct RtLoad {     // one fragment brought to the device
     uint8_t* to;
 };
 
+// One loaded fragment against its name (dig, name: 32 bytes each; null name: taken as given): a good
+// one is entered in f at l.idx, another is kFragBad there.  The rule of the single-object calls and
+// of the batch alike.
+void rt_enter_frag(const RtLoad& l, const uint8_t* dig, const uint8_t* name, RtFrags& f, uint8_t* fst) {
+    if (name && std::memcmp(dig, name, 32) != 0) {
+        fst[l.idx] = kFragBad;
+        return;
+    }
+    f[l.idx] = l.to;
+}
+
+// ns segment digests against their names: a segment that differs is kSegMismatch; true when all match.
+bool rt_match_segs(const uint8_t* segd, const uint8_t* seg_names, uint64_t ns, uint8_t* sst) {
+    bool all = true;
+    for (uint64_t t = 0; t < ns; t++)
+        if (std::memcmp(segd + 32 * t, seg_names + 32 * t, 32) != 0) {
+            sst[t] = kSegMismatch;
+            all = false;
+        }
+    return all;
+}
+
 // 2. The fragments just loaded against their names (names + 32 * idx; null: taken as given), hashed
 // in one leaf launch: a good one is entered in f, another is kFragBad.
 int rt_check_frags(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<RtLoad>& loads, uint64_t frag,
@@ -78,14 +102,8 @@ int rt_check_frags(dm_ctx* c, Dev& d, hipStream_t s, const std::vector<RtLoad>& 
         for (size_t q = 0; q < loads.size(); q++) addrs[q] = reinterpret_cast<uint64_t>(loads[q].to);
         RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
     }
-    for (size_t q = 0; q < loads.size(); q++) {
-        const uint64_t i = loads[q].idx;
-        if (names && std::memcmp(dig.data() + 32 * q, names + 32 * i, 32) != 0) {
-            fst[i] = kFragBad;
-            continue;
-        }
-        f[i] = loads[q].to;
-    }
+    for (size_t q = 0; q < loads.size(); q++)
+        rt_enter_frag(loads[q], names ? dig.data() + 32 * q : nullptr, names ? names + 32 * loads[q].idx : nullptr, f, fst);
     return DM_OK;
 }
 
@@ -111,12 +129,7 @@ int rt_rebuild(dm_rs* r, Dev& d, hipStream_t s, const RtFrags& f, uint64_t ns, u
     std::vector<uint64_t> sa(ns);
     for (uint64_t t = 0; t < ns; t++) sa[t] = reinterpret_cast<uint64_t>(base + t * segment);
     RC_TRY(rt_hash(c, d, s, sa, segment, segd));
-    if (seg_names)
-        for (uint64_t t = 0; t < ns; t++)
-            if (std::memcmp(segd.data() + 32 * t, seg_names + 32 * t, 32) != 0) {
-                sst[t] = kSegMismatch;
-                res = Rebuild::kMismatch;
-            }
+    if (seg_names && !rt_match_segs(segd.data(), seg_names, ns, sst)) res = Rebuild::kMismatch;
     return DM_OK;
 }
 
@@ -357,6 +370,209 @@ int restore_buffer_call(dm_rs* r, const char* fn, const void* const* frags, cons
     return rc;
 }
 
+// ---- many objects in one pass (dm_restore_batch, the DM_BATCH_RESTORE batcher) ----
+
+// The batch as restore_batch_plan.hpp takes it.
+std::vector<dm_restore_plan::Obj> rb_objs(const dm_restore_obj* objs, uint64_t nobj) {
+    std::vector<dm_restore_plan::Obj> po(nobj);
+    for (uint64_t o = 0; o < nobj; o++) {
+        po[o].frags = objs[o].frags;
+        po[o].nseg = objs[o].nseg;
+        po[o].size = objs[o].size;
+        po[o].cipher = objs[o].cipher;
+        po[o].cipher_len = objs[o].cipher_len;
+        po[o].out = objs[o].out;
+    }
+    return po;
+}
+
+int rb_fail(dm_ctx* c, const dm_restore_plan::Error& e) {
+    return fail(c, e.code == dm_restore_plan::kEmpty ? DM_ERR_EMPTY : DM_ERR_INVALID, "%s", e.msg.c_str());
+}
+
+// Statuses of every object of a batch, [plan.nseg * total] and [plan.nseg] in the batch-wide
+// segment order; copied to the callers however the pass ends.
+struct RbStatus {
+    std::vector<uint8_t> fst, sst;
+    RbStatus(const dm_restore_plan::Plan& p) : fst(p.nseg * (uint64_t)p.total, 0), sst(p.nseg, 0) {}
+    void copy_out(const dm_restore_plan::Plan& p, const dm_restore_obj* objs) const {
+        for (size_t o = 0; o < p.obj.size(); o++) {
+            const uint64_t s0 = p.obj[o].seg0, ns = objs[o].nseg;
+            if (objs[o].frag_status) std::memcpy(objs[o].frag_status, fst.data() + s0 * p.total, ns * p.total);
+            if (objs[o].seg_status) std::memcpy(objs[o].seg_status, sst.data() + s0, ns);
+        }
+    }
+};
+
+// The pass of dm_restore_batch over a checked batch and its plan, on d.stream; synchronous.  The
+// steps are restore_buffer's, each ONE launch over every object still alive: an object that fails a
+// step keeps the statuses restore_buffer would give it and is left out of the steps after.
+int restore_batch_host(dm_rs* r, Dev& d, const dm_restore_obj* objs, const std::vector<dm_restore_plan::Obj>& po,
+                       const dm_restore_plan::Plan& p, RbStatus& st, int* ok) {
+    dm_ctx* c = r->c;
+    hipStream_t s = d.stream;
+    RC_TRY(begin_call(c, d, s));
+    const uint64_t nobj = p.obj.size(), segment = p.segment, frag = p.frag;
+    const int k = p.k, total = p.total;
+    DevBuf& work = rs_ln(r, d).work;
+    // the whole batch must fit: no splitting, and no growth that fails half way through the staging
+    {
+        const bool gd = p.data_bytes > d.data.cap, gw = p.work_bytes > work.cap;   // a grown buffer's old block is freed first
+        const uint64_t grow = (gd ? p.data_bytes : 0) + (gw ? p.work_bytes : 0);
+        const uint64_t back = (gd ? d.data.cap : 0) + (gw ? work.cap : 0);
+        size_t fr = 0, tot = 0;
+        if (grow && free_on(d.id, &fr, &tot) && fr + back < grow + kMallocHeadroom)
+            return fail(c, DM_ERR_NOMEM, "dm_restore_batch: the batch needs %llu bytes of device memory, %llu are free",
+                        (unsigned long long)p.device_bytes(), (unsigned long long)fr);
+    }
+    HIP_TRY(d.data.ensure(p.data_bytes));
+    HIP_TRY(work.ensure(p.work_bytes));
+    std::vector<CipherKey> keys(p.keys.size());
+    for (size_t e = 0; e < keys.size(); e++) RC_TRY(cipher_key(c, p.keys[e].bytes, p.keys[e].len, keys[e]));
+    std::vector<uint8_t> alive(nobj, 1);
+    // 1. one staging: data fragments to their final place, parity fragments packed into scratch
+    RtFrags have(p.nseg * (uint64_t)total, nullptr);
+    std::vector<RtLoad> loads;          // idx: batch-wide fragment index
+    std::vector<uint64_t> load_obj;
+    for (uint64_t o = 0; o < nobj; o++) {
+        const dm_restore_plan::ObjPlan& q = p.obj[o];
+        uint64_t slot = 0;
+        for (uint64_t t = 0; t < objs[o].nseg; t++)
+            for (int j = 0; j < total; j++) {
+                const void* src = objs[o].frags[t * total + j];
+                if (!src) continue;
+                uint8_t* to = j < k ? d.data.u8() + q.obj_off + t * segment + (uint64_t)j * frag
+                                    : work.u8() + q.par_off + (slot++) * frag;
+                HIP_TRY(hipMemcpyAsync(to, src, frag, hipMemcpyHostToDevice, s));
+                loads.push_back({(q.seg0 + t) * total + j, to});
+                load_obj.push_back(o);
+            }
+    }
+    // 2. one leaf launch over every fragment of the objects that asked for the fragment check
+    {
+        std::vector<uint64_t> addrs;
+        std::vector<size_t> which;
+        for (size_t i = 0; i < loads.size(); i++) {
+            const dm_restore_obj& x = objs[load_obj[i]];
+            if ((x.flags & DM_RESTORE_VERIFY_FRAGMENTS) && x.frag_names) {
+                addrs.push_back(reinterpret_cast<uint64_t>(loads[i].to));
+                which.push_back(i);
+            } else {
+                rt_enter_frag(loads[i], nullptr, nullptr, have, st.fst.data());
+            }
+        }
+        std::vector<uint8_t> dig;
+        RC_TRY(rt_hash(c, d, s, addrs, frag, dig));
+        for (size_t a = 0; a < which.size(); a++) {
+            const RtLoad& l = loads[which[a]];
+            const uint64_t o = load_obj[which[a]], local = l.idx - p.obj[o].seg0 * total;
+            rt_enter_frag(l, dig.data() + 32 * a, objs[o].frag_names + 32 * local, have, st.fst.data());
+        }
+    }
+    // 3. statuses per object; one restore launch over every segment of the objects that can be rebuilt
+    RestoreBatch b{r->mat.data(), k, r->m};
+    for (uint64_t o = 0; o < nobj; o++) {
+        const dm_restore_plan::ObjPlan& q = p.obj[o];
+        const uint64_t f0 = q.seg0 * total;
+        if (!rt_select(k, total, objs[o].nseg, have.data() + f0, st.fst.data() + f0, st.sst.data() + q.seg0)) {
+            alive[o] = 0;
+            continue;
+        }
+        for (uint64_t t = 0; t < objs[o].nseg; t++)
+            RC_TRY(plan_status(c, restore_add(b, have.data() + f0 + t * total, d.data.u8() + q.obj_off + t * segment, frag), k));
+    }
+    RC_TRY(rs_desc_launch(r, d, s, b, frag / 16));
+    // 4. one leaf launch over the segments of the objects that asked for segment or fid checks; the
+    // fid objects come first, so that their digests are one run of d.leaves and reduce in place
+    {
+        std::vector<uint64_t> order, first(1, 0), sa;
+        auto vseg = [&](uint64_t o) { return (objs[o].flags & DM_RESTORE_VERIFY_SEGMENTS) && objs[o].seg_names; };
+        auto vfid = [&](uint64_t o) { return (objs[o].flags & DM_RESTORE_VERIFY_FID) && objs[o].fid; };
+        for (uint64_t o = 0; o < nobj; o++)
+            if (alive[o] && vfid(o)) {
+                order.push_back(o);
+                first.push_back(first.back() + objs[o].nseg);
+            }
+        const uint64_t nfid = order.size();
+        for (uint64_t o = 0; o < nobj; o++)
+            if (alive[o] && !vfid(o) && vseg(o)) order.push_back(o);
+        for (uint64_t o : order)
+            for (uint64_t t = 0; t < objs[o].nseg; t++)
+                sa.push_back(reinterpret_cast<uint64_t>(d.data.u8() + p.obj[o].obj_off + t * segment));
+        if (!sa.empty()) {
+            const uint64_t T = sa.size();
+            const std::vector<uint64_t> lens(T, segment);
+            dm::LeafArgs la;
+            RC_TRY(table_args(c, d, s, sa.data(), lens.data(), T, (nfid + 1) * 12 + 2048, &la));
+            RC_TRY(launch_leaves(c, d, s, la, true, true, pick_leaf_kernel(c, d, T)));
+            std::vector<uint8_t> segd(32 * T), roots(32 * nfid);
+            HIP_TRY(hipMemcpyAsync(segd.data(), d.leaves.p, 32 * T, hipMemcpyDeviceToHost, s));
+            if (nfid) {
+                uint8_t* dfid = work.u8() + p.fid_base;
+                RC_TRY(batch_roots_from_leaves(c, d, s, d.leaves.u8(), first, dfid));
+                HIP_TRY(hipMemcpyAsync(roots.data(), dfid, 32 * nfid, hipMemcpyDeviceToHost, s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));
+            uint64_t at = 0;
+            for (size_t i = 0; i < order.size(); i++) {
+                const uint64_t o = order[i], ns = objs[o].nseg;
+                if (vseg(o) && !rt_match_segs(segd.data() + 32 * at, objs[o].seg_names, ns, st.sst.data() + p.obj[o].seg0))
+                    alive[o] = 0;
+                if (alive[o] && i < nfid && std::memcmp(roots.data() + 32 * i, objs[o].fid, 32) != 0) alive[o] = 0;
+                at += ns;
+            }
+        }
+    }
+    // 5. one keyed decrypt launch over the segments of the encrypted objects still alive
+    {
+        const std::vector<dm_restore_plan::Chain> ch = dm_restore_plan::decrypt_chains(p, po.data(), alive.data());
+        if (!ch.empty()) {
+            std::vector<KeyedDChain> kc(ch.size());
+            for (size_t i = 0; i < ch.size(); i++)
+                kc[i] = KeyedDChain{d.data.u8() + ch[i].in_off, work.u8() + ch[i].out_off, ch[i].key};
+            uint8_t* pad_ok = work.u8() + p.pad_base;
+            RC_TRY(launch_aes_decrypt_keyed(c, d, s, keys, kc, segment, pad_ok));
+            // 6. the padding verdicts come back, and only then any bytes
+            std::vector<uint8_t> pad(ch.size());
+            HIP_TRY(hipMemcpyAsync(pad.data(), pad_ok, ch.size(), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            for (size_t i = 0; i < ch.size(); i++)
+                if (pad[i] != 1) {
+                    st.sst[p.obj[ch[i].obj].seg0 + ch[i].seg] = kSegBadPadding;
+                    alive[ch[i].obj] = 0;
+                }
+        }
+    }
+    for (uint64_t o = 0; o < nobj; o++) {
+        if (!alive[o]) continue;
+        const dm_restore_plan::ObjPlan& q = p.obj[o];
+        const uint8_t* src = q.key < 0 ? d.data.u8() + q.obj_off : work.u8() + q.plain_off;
+        HIP_TRY(hipMemcpyAsync(objs[o].out, src, objs[o].size, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint64_t o = 0; o < nobj; o++) ok[o] = alive[o];
+    return DM_OK;
+}
+
+// Plan, pass and statuses of a batch whose arguments have been checked; what dm_restore_batch and
+// the batcher's workers both run (the caller holds the lane).
+int restore_batch_run(dm_rs* r, Dev& d, const dm_restore_obj* objs, uint64_t nobj, uint64_t segment, int* ok) {
+    for (uint64_t o = 0; o < nobj; o++) ok[o] = 0;
+    const std::vector<dm_restore_plan::Obj> po = rb_objs(objs, nobj);
+    const dm_restore_plan::Plan p = dm_restore_plan::plan(po.data(), nobj, segment, r->k, r->m);
+    RbStatus st(p);
+    const int rc = restore_batch_host(r, d, objs, po, p, st, ok);
+    // no copy from or to a caller's memory stays queued, whichever way the pass ends
+    if (rc != DM_OK) {
+        (void)hipStreamSynchronize(d.stream);
+        for (uint64_t o = 0; o < nobj; o++) ok[o] = 0;
+    }
+    st.copy_out(p, objs);
+    if (d.data.cap > kFpKeepBytes) r->c->reaper.put(d.id, d.data);
+    if (rs_ln(r, d).work.cap > kFpKeepBytes) r->c->reaper.put(d.id, rs_ln(r, d).work);
+    return rc;
+}
+
 std::mutex g_plan_mu;
 std::map<int, std::vector<uint8_t>> g_plan_mats;   // data * 16 + parity -> coding matrix
 
@@ -429,6 +645,19 @@ int dm_restore_cipher_buffer(dm_rs* r, const void* const* frags, const uint8_t* 
     CipherKey key;
     return restore_buffer_call(r, "dm_restore_cipher_buffer", frags, frag_names, seg_names, fid, nseg, size, segment,
                                flags, &key, cipher, cipher_len, out, frag_status, seg_status, ok);
+}
+
+int dm_restore_batch(dm_rs* r, const dm_restore_obj* objs, uint64_t nobj, uint64_t segment, int* ok) {
+    if (!r) return bad_arg();
+    dm_ctx* c = r->c;
+    const int g = rs_lane(c);
+    CallLock lk(c, g, kReserved);
+    RC_TRY(rs_narrow(r, "dm_restore_batch"));
+    if (nobj == 0) return DM_OK;
+    if (!objs || !ok) return fail(c, DM_ERR_INVALID, "dm_restore_batch: null argument");
+    if (const dm_restore_plan::Error e = dm_restore_plan::check(rb_objs(objs, nobj).data(), nobj, segment, r->k))
+        return rb_fail(c, e);
+    return restore_batch_run(r, c->devs[g], objs, nobj, segment, ok);
 }
 
 int dm_retrieve_file(dm_rs* r, const char* fragdir, const uint8_t* frag_names, const uint8_t* seg_names,

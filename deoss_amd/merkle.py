@@ -13,7 +13,7 @@ import ctypes
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
-from ._lib import (DM_ERR_EMPTY, DM_ERR_INVALID, AesChain, AesKey, AesWindow, DeossMerkleError, RangeWindow,
+from ._lib import (DM_ERR_EMPTY, DM_ERR_INVALID, AesChain, AesDChain, AesKey, AesWindow, DeossMerkleError, RangeWindow,
                    load_library)
 
 RANGE_NO_PADDING_CHECK = 8                                          # DM_RANGE_NO_PADDING_CHECK
@@ -267,6 +267,28 @@ class MerkleContext:
         self._check(self._L.dm_aes_cbc_encrypt_keyed_device_async(self._h, karr, len(keys), carr, len(chains), plain,
                                                                   ctypes.c_void_p(stream or None)),
                     "dm_aes_cbc_encrypt_keyed_device_async")
+
+    def aes_cbc_decrypt_keyed_device_async(self, keys, chains, cipher_bytes: int, pad_ok_ptr: int,
+                                           stream: int = 0) -> None:
+        """``dm_aes_cbc_decrypt_keyed_device_async``: ONE launch over ``chains`` = [(dev_in, dev_out,
+        key_index)], chain c's ``cipher_bytes`` decrypted out of place under ``keys[key_index]`` =
+        (key bytes, iv) into cipher_bytes - 16 plaintext bytes, its padding verdict to
+        ``pad_ok_ptr[c]``; keys of different lengths may share the launch."""
+        keep = []
+        karr = (AesKey * max(len(keys), 1))()
+        for i, (key, iv) in enumerate(keys):
+            if len(iv) != 16:
+                raise DeossMerkleError(DM_ERR_INVALID, "iv must be 16 bytes")
+            kb = ctypes.create_string_buffer(bytes(key), max(len(key), 1))
+            keep.append(kb)
+            karr[i].key = ctypes.addressof(kb)
+            karr[i].key_len = len(key)
+            karr[i].iv[:] = bytes(iv)
+        carr = (AesDChain * max(len(chains), 1))(*[AesDChain(i or None, o or None, k, 0) for i, o, k in chains])
+        self._check(self._L.dm_aes_cbc_decrypt_keyed_device_async(self._h, karr, len(keys), carr, len(chains),
+                                                                  cipher_bytes, ctypes.c_void_p(pad_ok_ptr or None),
+                                                                  ctypes.c_void_p(stream or None)),
+                    "dm_aes_cbc_decrypt_keyed_device_async")
 
     def aes_cbc_decrypt_device_async(self, key: bytes, iv: bytes, dev_in: int, in_stride: int, cipher_bytes: int,
                                      nseg: int, dev_out: int, out_stride: int, dev_pad_ok: int,

@@ -32,7 +32,7 @@ import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, DM_ERR_IO, DeossMerkleError
+from ._lib import DM_ERR_EMPTY, DM_ERR_INVALID, DM_ERR_IO, DeossMerkleError, RestoreObj, restore_obj_fields
 from .merkle import RANGE_NO_PADDING_CHECK, MerkleContext, range_plan  # noqa: F401
 from .reedsolomon import DATA_SHARDS, PAR_SHARDS, Encoder
 
@@ -62,6 +62,18 @@ class SegmentDataInfo:
     """chain.SegmentDataInfo: the segment's path name and its fragments' path names."""
     SegmentHash: str = ""
     FragmentHash: List[str] = field(default_factory=list)
+
+
+@dataclass
+class RestoreObject:
+    """One object of :meth:`Processor.restore_batch`: ``restore_buffer``'s arguments and a cipher."""
+    frags: list
+    size: int
+    frag_names: Optional[bytes] = None
+    seg_names: Optional[bytes] = None
+    fid: Optional[bytes] = None
+    flags: int = RESTORE_VERIFY_ALL
+    cipher: bytes = b""
 
 
 class Processor:
@@ -261,6 +273,31 @@ class Processor:
                         "dm_restore_buffer")
         data = dst.raw[:size] if (ok.value and out is None) else None
         return bool(ok.value), data, fst.raw[:nseg * total], sst.raw[:nseg]
+
+    def restore_batch(self, objects) -> List[Tuple[bool, Optional[bytes], bytes, bytes]]:
+        """``dm_restore_batch``: many objects restored and verified in one pass.  ``objects``:
+        :class:`RestoreObject` items or dicts with ``restore_buffer``'s arguments (``frags``, ``size``,
+        ``frag_names``, ``seg_names``, ``fid``, ``flags``) and a ``cipher`` each.  Returns one (ok,
+        data or None, fragment statuses, segment statuses) per object, each what ``restore_buffer``
+        gives for that object alone; an argument error raises, naming the object."""
+        objs = [RestoreObject(**o) if isinstance(o, dict) else o for o in objects]
+        n = len(objs)
+        if n == 0:
+            return []
+        total = self.k + self.m
+        arr = (RestoreObj * n)()
+        parts = []
+        for i, o in enumerate(objs):
+            f = restore_obj_fields(o.frags, o.size, o.frag_names, o.seg_names, o.fid, o.flags, _cipher_bytes(o.cipher),
+                                    total, self.frag)
+            arr[i] = f[0]
+            parts.append(f)
+        ok = (ctypes.c_int * n)()
+        self._check(self.ctx._L.dm_restore_batch(self.enc._h, arr, n, self.segment, ok), "dm_restore_batch")
+        res = []
+        for i, (_o, nseg, out, fst, sst, _keep) in enumerate(parts):
+            res.append((bool(ok[i]), out.raw[:objs[i].size] if ok[i] else None, fst.raw[:nseg * total], sst.raw[:nseg]))
+        return res
 
     def retrieve_file(self, fragdir: str, frag_names: bytes, size: int, out_path: str,
                       seg_names: Optional[bytes] = None, fid: Optional[bytes] = None,

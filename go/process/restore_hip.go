@@ -23,6 +23,7 @@ import (
 	"fmt"
 	"path/filepath"
 	"runtime"
+	"sync"
 	"unsafe"
 
 	"github.com/CESSProject/cess-go-sdk/chain"
@@ -103,12 +104,23 @@ func RestoreFile(fragDir string, segs []chain.SegmentDataInfo, size uint64, outP
 	return nil
 }
 
-// RestoreFragments is RestoreFile for bytes already in memory: frags[s][j] is fragment j of segment
-// s (data fragments first) or nil when it was not fetched.  Returns the file's size bytes.
-func RestoreFragments(frags [][][]byte, segs []chain.SegmentDataInfo, size uint64) ([]byte, error) {
-	if err := gpu(); err != nil {
-		return nil, err
-	}
+// restoreArgs is an in-memory restore as the C calls take it: the decoded names and the table of
+// fragment pointers.  The table lives in C memory (cgo forbids Go pointers to Go pointers); the
+// fragments themselves stay pinned until release.
+type restoreArgs struct {
+	segn, fragn []byte
+	table       *[1 << 28]unsafe.Pointer
+	pin         runtime.Pinner
+}
+
+func (a *restoreArgs) release() {
+	a.pin.Unpin()
+	C.free(unsafe.Pointer(a.table))
+}
+
+// restoreInputs checks frags[s][j] (fragment j of segment s, nil = not fetched) against segs and
+// builds the arguments; the caller defers release() when err is nil.
+func restoreInputs(frags [][][]byte, segs []chain.SegmentDataInfo, size uint64) (*restoreArgs, error) {
 	total := chain.DataShards + chain.ParShards
 	frag := int(chain.SegmentSize) / chain.DataShards
 	if len(segs) == 0 || len(frags) != len(segs) || size == 0 {
@@ -118,18 +130,15 @@ func RestoreFragments(frags [][][]byte, segs []chain.SegmentDataInfo, size uint6
 	if err != nil {
 		return nil, err
 	}
-	// the pointer table lives in C memory (cgo forbids Go pointers to Go pointers); the fragments
-	// themselves are pinned for the call
 	n := len(segs) * total
 	table := (*[1 << 28]unsafe.Pointer)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
 	if table == nil {
 		return nil, errors.New("restore: out of memory")
 	}
-	defer C.free(unsafe.Pointer(table))
-	var pin runtime.Pinner
-	defer pin.Unpin()
+	a := &restoreArgs{segn: segn, fragn: fragn, table: table}
 	for s := range frags {
 		if len(frags[s]) != total {
+			a.release()
 			return nil, fmt.Errorf("restore: segment %d has %d fragment slots, want %d", s, len(frags[s]), total)
 		}
 		for j, f := range frags[s] {
@@ -137,24 +146,100 @@ func RestoreFragments(frags [][][]byte, segs []chain.SegmentDataInfo, size uint6
 				continue
 			}
 			if len(f) != frag {
+				a.release()
 				return nil, fmt.Errorf("restore: fragment %d of segment %d has %d bytes, want %d", j, s, len(f), frag)
 			}
-			pin.Pin(&f[0])
+			a.pin.Pin(&f[0])
 			table[s*total+j] = unsafe.Pointer(&f[0])
 		}
 	}
+	return a, nil
+}
+
+// RestoreFragments is RestoreFile for bytes already in memory: frags[s][j] is fragment j of segment
+// s (data fragments first) or nil when it was not fetched.  Returns the file's size bytes.
+func RestoreFragments(frags [][][]byte, segs []chain.SegmentDataInfo, size uint64) ([]byte, error) {
+	if err := gpu(); err != nil {
+		return nil, err
+	}
+	in, err := restoreInputs(frags, segs, size)
+	if err != nil {
+		return nil, err
+	}
+	defer in.release()
 	out := make([]byte, size)
 	rs := <-pipes
 	defer func() { pipes <- rs }()
 	var ok C.int
 	runtime.LockOSThread()
 	defer runtime.UnlockOSThread()
-	rc := C.dm_restore_buffer(rs, (*unsafe.Pointer)(unsafe.Pointer(table)), (*C.uint8_t)(unsafe.Pointer(&fragn[0])),
-		(*C.uint8_t)(unsafe.Pointer(&segn[0])), nil, C.uint64_t(len(segs)), C.uint64_t(size),
+	rc := C.dm_restore_buffer(rs, (*unsafe.Pointer)(unsafe.Pointer(in.table)), (*C.uint8_t)(unsafe.Pointer(&in.fragn[0])),
+		(*C.uint8_t)(unsafe.Pointer(&in.segn[0])), nil, C.uint64_t(len(segs)), C.uint64_t(size),
 		C.uint64_t(chain.SegmentSize), C.int(C.DM_RESTORE_VERIFY_FRAGMENTS|C.DM_RESTORE_VERIFY_SEGMENTS),
 		unsafe.Pointer(&out[0]), nil, nil, &ok)
 	if rc != C.DM_OK {
 		return nil, restoreError(rc)
+	}
+	if ok == 0 {
+		return nil, ErrRestore
+	}
+	return out, nil
+}
+
+var (
+	restoreOnce    sync.Once
+	restoreBatcher *C.dm_batcher // in-memory restores from every goroutine
+	restoreInitErr error
+)
+
+// restoreQueue makes the process-wide DM_BATCH_RESTORE batcher on first use: every visible GPU, 4
+// worker slots each, 2 ms linger, as the upload side's batcher (DESIGN.md §6.9, §6.13).
+func restoreQueue() error {
+	if err := gpu(); err != nil {
+		return err
+	}
+	restoreOnce.Do(func() {
+		runtime.LockOSThread()
+		defer runtime.UnlockOSThread()
+		if rc := C.dm_batcher_create(nil, 0, C.DM_BATCH_RESTORE, C.uint64_t(chain.SegmentSize), C.int(chain.DataShards),
+			C.int(chain.ParShards), 0, 0, 0, 2000, &restoreBatcher); rc != C.DM_OK {
+			restoreInitErr = errors.New(C.GoString(C.dm_batcher_last_error()))
+		}
+	})
+	return restoreInitErr
+}
+
+// RestoreBuffers is RestoreFragments through the process-wide restore batcher: download handlers
+// (GET /file/download, GET /file/open) run one goroutine per request, and whatever they have queued
+// becomes ONE verified GPU pass (dm_batcher_restore -> dm_restore_batch): many small downloads
+// share one pass (measured: DESIGN.md §6.13).  frags, segs and size as RestoreFragments; cipher == "" is a plain
+// object, otherwise the object is decrypted on the GPU after its checks (the scheme is recalled,
+// not pinned: DESIGN.md §6.14) and size counts plaintext bytes.  A request that fails its checks
+// returns ErrRestore and changes nothing for the requests that shared its pass.
+func RestoreBuffers(frags [][][]byte, segs []chain.SegmentDataInfo, size uint64, cipher string) ([]byte, error) {
+	if err := restoreQueue(); err != nil {
+		return nil, err
+	}
+	in, err := restoreInputs(frags, segs, size)
+	if err != nil {
+		return nil, err
+	}
+	defer in.release()
+	var ckey unsafe.Pointer
+	if cipher != "" {
+		ckey = C.CBytes([]byte(cipher))
+		defer C.free(ckey)
+	}
+	out := make([]byte, size)
+	var ok C.int
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	rc := C.dm_batcher_restore(restoreBatcher, (*unsafe.Pointer)(unsafe.Pointer(in.table)), (*C.uint8_t)(unsafe.Pointer(&in.fragn[0])),
+		(*C.uint8_t)(unsafe.Pointer(&in.segn[0])), nil, C.uint64_t(len(segs)), C.uint64_t(size),
+		C.int(C.DM_RESTORE_VERIFY_FRAGMENTS|C.DM_RESTORE_VERIFY_SEGMENTS), ckey, C.uint64_t(len(cipher)),
+		unsafe.Pointer(&out[0]), nil, nil, &ok)
+	if rc != C.DM_OK {
+		return nil, batcherError(rc)
 	}
 	if ok == 0 {
 		return nil, ErrRestore

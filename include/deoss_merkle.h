@@ -450,6 +450,26 @@ int dm_aes_cbc_encrypt_keyed_device_async(dm_ctx *ctx, const dm_aes_key *keys, u
 int dm_aes_cbc_decrypt_device_async(dm_ctx *ctx, const void *key, uint64_t key_len, const uint8_t iv[16],
                                     const void *dev_in, uint64_t in_stride, uint64_t cipher_bytes, uint64_t nseg,
                                     void *dev_out, uint64_t out_stride, void *dev_pad_ok, void *stream);
+/* Decrypt with a key per chain: nchain chains anywhere in device memory (no common stride), chain c's
+ * cipher_bytes at chains[c].dev_in become cipher_bytes - 16 plaintext bytes at chains[c].dev_out
+ * under keys[chains[c].key_index] (dm_aes_key as above), and dev_pad_ok[c] is its padding verdict --
+ * ONE launch whatever the mix of keys and key lengths (a coalesced batch holds different clients'
+ * downloads: dm_restore_batch).  The result equals dm_aes_cbc_decrypt_device_async per key.  The
+ * round keys travel in a table in the call lane's scratch, zeroed in stream order right after the
+ * kernel; both arrays may be released on return.  A key length other than 16, 24 or 32 is
+ * DM_ERR_INVALID "key <i>: cipher must be 16, 24 or 32 bytes"; in and out must be non-null and 16-byte
+ * aligned, key_index < nkeys, cipher_bytes % 16 == 0 and cipher_bytes >= 32 (else DM_ERR_INVALID,
+ * nothing runs).  Not checked, the caller's to keep: no chain's output overlaps any chain's input or
+ * another's output.  nchain == 0 is a no-op. */
+typedef struct dm_aes_dchain {
+    const void *dev_in;
+    void *dev_out;
+    uint32_t key_index;
+    uint32_t reserved;
+} dm_aes_dchain;
+int dm_aes_cbc_decrypt_keyed_device_async(dm_ctx *ctx, const dm_aes_key *keys, uint64_t nkeys,
+                                          const dm_aes_dchain *chains, uint64_t nchain, uint64_t cipher_bytes,
+                                          void *dev_pad_ok, void *stream);
 /* dm_process_buffer with a cipher (synchronous): outputs as there, over nseg = ceil(len / (segment - 16))
  * segments of ciphertext. */
 int dm_process_cipher_buffer(dm_rs *rs, const void *host, uint64_t len, uint64_t segment, const void *cipher,
@@ -490,6 +510,36 @@ int dm_restore_cipher_buffer(dm_rs *rs, const void *const *frags, const uint8_t 
                              const uint8_t *fid, uint64_t nseg, uint64_t size, uint64_t segment, int flags,
                              const void *cipher, uint64_t cipher_len, void *out, uint8_t *frag_status,
                              uint8_t *seg_status, int *ok);
+/* Many objects restored and verified in ONE pass (synchronous, one call lane): download handlers run
+ * one goroutine per request, and a verified restore costs two rounds of latency-bound SHA-256 chains
+ * whether it carries 1 segment or 256.  Each object has its own fragments, names, flags and cipher
+ * (fields as the arguments of dm_restore_buffer / dm_restore_cipher_buffer; cipher NULL or
+ * cipher_len 0: a plain object of the same batch; `size` counts plaintext bytes with a cipher).
+ * Whatever nobj: one staging of all fragments, one leaf launch over every fragment of the objects
+ * that asked for the fragment check, one restore launch over every segment that can still be
+ * rebuilt, one leaf launch over the segments of the objects that asked for segment or fid checks
+ * (and their fids), one keyed decrypt launch (dm_aes_cbc_decrypt_keyed_device_async) over the
+ * encrypted objects' segments; the padding verdicts come back, and only then the bytes of the
+ * objects that held.  Object i's ok[i], out, frag_status and seg_status are exactly what
+ * dm_restore_buffer (no cipher) or dm_restore_cipher_buffer (cipher) gives for that object alone: too
+ * few good fragments, a segment or fid mismatch or a bad padding block set that object's ok[i] = 0,
+ * leave its `out` untouched and change nothing for any other object (its segments are left out of
+ * the later launches).  Everything is checked before anything runs: an argument error is
+ * DM_ERR_INVALID or DM_ERR_EMPTY naming the object ("object <i>: ..."), and nothing is written.
+ * A batch that does not fit in free device memory is DM_ERR_NOMEM (the call does not split).  On
+ * any failing return code every ok[i] is 0 and no copy from or to caller memory stays queued.
+ * nobj == 0 is a no-op (DM_OK). */
+typedef struct dm_restore_obj {
+    const void *const *frags;          /* nseg x (data + parity) host pointers, NULL = not downloaded */
+    const uint8_t *frag_names, *seg_names, *fid;   /* each nullable, as dm_restore_buffer */
+    uint64_t nseg, size;               /* size: plaintext bytes when cipher_len != 0 */
+    int flags;                         /* DM_RESTORE_VERIFY_*, per object */
+    const void *cipher;
+    uint64_t cipher_len;               /* NULL / 0: a plain object of the same batch */
+    void *out;                         /* size bytes, written only when ok[i] = 1 */
+    uint8_t *frag_status, *seg_status; /* nullable */
+} dm_restore_obj;
+int dm_restore_batch(dm_rs *rs, const dm_restore_obj *objs, uint64_t nobj, uint64_t segment, int *ok);
 
 /* ---- ranged restore: any byte range from just the fragments that cover it (the HTTP Range of
  * GET /file/open, node/fileHandler.go:399-545, which otherwise restores the whole object first).
@@ -652,11 +702,12 @@ int dm_verify_paths(dm_ctx *ctx, const void *const *contents, const uint64_t *le
  * `slots` worker contexts so one batch collects while another runs.  Results are identical to
  * the single-object calls (dm_root_buffer / dm_process_buffer). */
 typedef struct dm_batcher dm_batcher;
-enum { DM_BATCH_ROOT = 0, DM_BATCH_PROCESS = 1 };
+enum { DM_BATCH_ROOT = 0, DM_BATCH_PROCESS = 1, DM_BATCH_RESTORE = 2 };
 /* devs / ndev: GPUs to serve from (devs NULL: every visible GPU); objects are independent, so
  * requests spread over the GPUs with no exchange.  mode ROOT: unit = chunk size (each request:
  * NewHashTreeFromBuffer); PROCESS: unit = segment size with data/parity shards (each request:
- * FullProcessing).  slots (0 = 4) worker contexts per GPU; max_leaves / max_bytes per batch
+ * FullProcessing); RESTORE: unit = segment size with data/parity shards (each request: a verified
+ * restore from fragments in memory, dm_batcher_restore).  slots (0 = 4) worker contexts per GPU; max_leaves / max_bytes per batch
  * (0 = 4096 leaves / 16 GiB); linger_us: how long a free worker holds a burst open for more
  * requests, counted from the oldest queued request's arrival (0 = at once).  While other slots
  * are running batches the wait grows with their share (the last free slot of 4 waits 9/256 of
@@ -677,6 +728,16 @@ int dm_batcher_process(dm_batcher *b, const void *host, uint64_t len, void *frag
  * request is queued, so a bad cipher fails its own call only. */
 int dm_batcher_process_cipher(dm_batcher *b, const void *host, uint64_t len, const void *cipher, uint64_t cipher_len,
                               void *frags_out, uint8_t *seg_hashes, uint8_t *frag_hashes, uint8_t fid[32]);
+/* A DM_BATCH_RESTORE batcher: blocking, thread-safe; arguments and outputs as dm_restore_buffer (cipher
+ * NULL or cipher_len 0) / dm_restore_cipher_buffer with the batcher's segment size.  Download handlers
+ * (GET /file/download, GET /file/open) run one goroutine per request; whatever is queued becomes ONE
+ * dm_restore_batch pass (what that saves: DESIGN.md section 6.13).  nseg, size, the cipher's
+ * length ("cipher must be 16, 24 or 32 bytes") and the segment size are checked before the request is
+ * queued, so a bad request fails its own call only; a failed verification is that request's
+ * *ok = 0, not an error of the batch. */
+int dm_batcher_restore(dm_batcher *b, const void *const *frags, const uint8_t *frag_names, const uint8_t *seg_names,
+                       const uint8_t *fid, uint64_t nseg, uint64_t size, int flags, const void *cipher,
+                       uint64_t cipher_len, void *out, uint8_t *frag_status, uint8_t *seg_status, int *ok);
 /* Requests served, batches launched, largest batch (requests). */
 int dm_batcher_stats(dm_batcher *b, uint64_t *requests, uint64_t *batches, uint64_t *max_batch);
 /* Message of the calling thread's last failing dm_batcher_* call. */

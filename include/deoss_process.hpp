@@ -337,6 +337,67 @@ inline std::optional<Error> RestoreFile(const std::string& fragdir, const std::v
     return std::nullopt;
 }
 
+// RestoreBatch (go/process/restore_hip.go RestoreBuffers, for a caller that already holds several
+// downloads): many objects restored from fragments in memory and verified in ONE dm_restore_batch
+// pass -- one staging, one leaf launch over the fragments, one restore launch, one leaf launch over
+// the segments, one keyed decrypt launch whatever the mix of ciphers.  Per object what
+// dm_restore_buffer / dm_restore_cipher_buffer give for it alone; an object that fails its checks
+// has ok = false and no data, and changes nothing for the others.  Concurrent handlers with one
+// download each take dm_batcher_restore.  With a cipher: PARITY-UNPINNED as above.
+struct RestoreObject {
+    std::vector<const void*> frags;                    // nseg x (data + parity), nullptr = not downloaded
+    std::vector<uint8_t> frag_names, seg_names, fid;   // each may be empty: its check is skipped
+    uint64_t size = 0;                                 // plaintext bytes when there is a cipher
+    int flags = DM_RESTORE_VERIFY_ALL;
+    std::string cipher;
+};
+
+struct RestoreOutput {
+    bool ok = false;
+    std::vector<uint8_t> data, frag_status, seg_status;
+};
+
+using RestoreBatchResult = std::pair<std::vector<RestoreOutput>, std::optional<Error>>;
+
+inline RestoreBatchResult RestoreBatch(const std::vector<RestoreObject>& objs, uint64_t segment = SegmentSize) {
+    auto& p = Pipelines::instance();
+    dm_rs* rs = p.pick();
+    if (!rs) return {{}, Error{p.status(), dm_strerror(p.status())}};
+    const uint64_t n = objs.size(), total = DataShards + ParShards;
+    std::vector<RestoreOutput> out(n);
+    std::vector<dm_restore_obj> arr(n);
+    std::vector<int> ok(n, 0);
+    for (uint64_t o = 0; o < n; o++) {
+        const RestoreObject& x = objs[o];
+        if (x.frags.size() % total) return {{}, Error{DM_ERR_INVALID, "process: need data + parity fragment entries per segment"}};
+        const uint64_t ns = x.frags.size() / total;
+        out[o].data.resize(x.size ? x.size : 1);
+        out[o].frag_status.resize(ns * total);
+        out[o].seg_status.resize(ns);
+        dm_restore_obj& a = arr[o];
+        a.frags = x.frags.data();
+        a.frag_names = x.frag_names.empty() ? nullptr : x.frag_names.data();
+        a.seg_names = x.seg_names.empty() ? nullptr : x.seg_names.data();
+        a.fid = x.fid.empty() ? nullptr : x.fid.data();
+        a.nseg = ns;
+        a.size = x.size;
+        a.flags = x.flags;
+        a.cipher = x.cipher.empty() ? nullptr : x.cipher.data();
+        a.cipher_len = x.cipher.size();
+        a.out = out[o].data.data();
+        a.frag_status = out[o].frag_status.data();
+        a.seg_status = out[o].seg_status.data();
+    }
+    const int rc = dm_restore_batch(rs, arr.data(), n, segment, ok.data());
+    if (rc != DM_OK) return {{}, last_error(rc)};
+    for (uint64_t o = 0; o < n; o++) {
+        out[o].ok = ok[o] != 0;
+        if (out[o].ok) out[o].data.resize(objs[o].size);
+        else out[o].data.clear();
+    }
+    return {std::move(out), std::nullopt};
+}
+
 // RestoreRange(fragDir, segs, size, off, length, cipher) (go/process/range_hip.go): bytes
 // [off, off + length) of the object for the HTTP Range of GET /file/open (node/fileHandler.go:399-545),
 // from just the fragments that cover them (dm_retrieve_range; dm_range_plan says which, so a gateway
